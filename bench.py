@@ -11,8 +11,16 @@ resident in HBM:
 Frames are sharded across ranks (weak scaling).  Default workload: C2 =
 BASELINE configs[1] (Shelf calibration, 5 cams, J=15, 128x240 -> 80x80x20).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the result line
+(frames/s, ms_per_step, the op's HBM roofline fraction from the HIP events of
+the timed steps).  `--full` adds every measurement that takes runs of its own:
+the rocprofv3 traffic counters, the measured copy rate and the design ceiling,
+the channels-last op, the one-frame latencies, the second-sequence cache build
+and the CPU baseline.  `--dump-outputs DIR` writes what the last timed step
+returned as DIR/<name>.npy (see dump_outputs).
 
 Without a launcher, `--gpus N > 1` starts `python -m torch.distributed.run
 --nproc-per-node N` on this same command line as a child process (this process
@@ -60,9 +68,16 @@ def parse(argv=None):
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=None, help="frames per GPU per step (default per workload)")
     ap.add_argument("--workload", default="c2")
-    ap.add_argument("--traffic", choices=["auto", "off"], default="auto",
-                    help="collect FETCH_SIZE/WRITE_SIZE with rocprofv3 child runs (N=1, rank 0)")
-    ap.add_argument("--cpu-baseline", choices=["on", "off"], default="on")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements (traffic counters, copy rate and ceiling, "
+                         "channels-last op, one-frame latencies, CPU baseline); a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (rank 0) as DIR/<name>.npy")
+    ap.add_argument("--traffic", choices=["auto", "off"], default=None,
+                    help="with --full: collect FETCH_SIZE/WRITE_SIZE with rocprofv3 child runs (N=1, rank 0; "
+                         "default auto)")
+    ap.add_argument("--cpu-baseline", choices=["on", "off"], default=None,
+                    help="with --full: time the reference's op order on the host cores (default on)")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="the CPU baseline's pool-share line (default: OMP_NUM_THREADS)")
     ap.add_argument("--graph", choices=["on", "off"], default="off",
@@ -78,7 +93,14 @@ def parse(argv=None):
     ap.add_argument("--on-the-fly", choices=["auto", "on", "off"], default="auto",
                     help="sampling coordinates from the cached grid (off) or projected in-kernel (on)")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if not args.full and (args.traffic == "auto" or args.cpu_baseline == "on"):
+        ap.error("--traffic auto and --cpu-baseline on are measurements of a --full run")
+    if args.traffic is None:
+        args.traffic = "auto" if args.full else "off"
+    if args.cpu_baseline is None:
+        args.cpu_baseline = "on" if args.full else "off"
+    return args
 
 
 # ---------------------------------------------------------------------------
@@ -514,6 +536,36 @@ def run_step(run_vox, run_post, collect, after_vox=None):
     return vals, flat, cols, collect(vals, flat)
 
 
+DUMP_ARRAY_BYTES = 8 << 20  # per written array; the step's seven at most stay under 64 MB in all
+DUMP_SEED = 20240
+
+
+def dump_outputs(out_dir, outputs):
+    """Write the step's outputs (name -> tensor) as out_dir/<name>.npy: floating
+    tensors as float32, integer ones (flat indices) as float64, which holds them
+    exactly.  An array above DUMP_ARRAY_BYTES is written as a fixed sample: its
+    flattened elements at sorted indices drawn from numpy's default_rng(DUMP_SEED)
+    over its element count, so two builds given the same arguments write the same
+    elements.  Returns {name: {"shape", "dtype", "sampled"}} for the result line."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, t in outputs.items():
+        t = t.detach()
+        dtype = torch.float32 if t.is_floating_point() else torch.float64
+        keep = DUMP_ARRAY_BYTES // (4 if dtype == torch.float32 else 8)
+        sampled = t.numel() > keep
+        if sampled:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, t.numel(), keep))
+            t = torch.take(t, torch.from_numpy(idx).to(t.device))
+        a = t.to(dtype).cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = {"shape": list(a.shape), "dtype": str(a.dtype), "sampled": bool(sampled)}
+    return written
+
+
 def main():
     # stdout carries only the JSON line: native libraries (RCCL prints a version
     # banner when a communicator comes up) write to fd 1 directly, so fd 1 points
@@ -621,17 +673,19 @@ def main():
     layer.prepare(hm, meta, cams, rt)
     torch.cuda.synchronize()
     first_ms = (time.perf_counter() - t0) * 1e3
-    seq_b = seq + "#second"
-    cams_b = {seq_b: cams[seq]}
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    t0 = time.perf_counter()
-    e0.record()
-    layer.prepare(hm_planar[:1], {"seq": [seq_b]}, cams_b, rt)
-    e1.record()
-    torch.cuda.synchronize()
-    cache_ms = {"first_call_ms": round(first_ms, 2), "sequence_build_ms": round((time.perf_counter() - t0) * 1e3, 3),
-                "sequence_build_gpu_ms": round(e0.elapsed_time(e1), 3),
+    cache_ms = {"first_call_ms": round(first_ms, 2),
                 "what": "grid" if not layer._project_on_the_fly(V) else "camera records (on-the-fly projection)"}
+    if args.full:
+        seq_b = seq + "#second"
+        cams_b = {seq_b: cams[seq]}
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0 = time.perf_counter()
+        e0.record()
+        layer.prepare(hm_planar[:1], {"seq": [seq_b]}, cams_b, rt)
+        e1.record()
+        torch.cuda.synchronize()
+        cache_ms["sequence_build_ms"] = round((time.perf_counter() - t0) * 1e3, 3)
+        cache_ms["sequence_build_gpu_ms"] = round(e0.elapsed_time(e1), 3)
 
     stream = torch.cuda.current_stream(dev)
     ev = []
@@ -652,13 +706,25 @@ def main():
 
     pool = []  # timing events, created before the timed region (creation is a HIP call per event)
 
-    def step(record):
+    kept = {}  # --dump-outputs: what the last timed step returned
+
+    def vox_kept():
+        kept["cube"], kept["xy"] = out = run_vox()
+        return out
+
+    def step(record, keep=False):
         if record:
             e0, e1 = pool.pop() if pool else (torch.cuda.Event(enable_timing=True),
                                               torch.cuda.Event(enable_timing=True))
             e0.record(stream)
             ev.append((e0, e1))
-        return run_step(run_vox, run_post, collect, after_vox=(lambda: e1.record(stream)) if record else None)[2]
+        out = run_step(vox_kept if keep else run_vox, run_post, collect,
+                       after_vox=(lambda: e1.record(stream)) if record else None)
+        if keep:
+            kept["vals"], kept["flat"], kept["cols"] = out[:3]
+            if out[3] is not None and world > 1:  # every rank's proposals, as the collective returned them
+                kept["all_vals"], kept["all_flat"] = out[3]
+        return out[2]
 
     note(f"warmup {args.warmup} + {args.steps} timed steps of {B} frames")
     for _ in range(args.warmup):
@@ -673,8 +739,9 @@ def main():
                 for _ in range(args.steps))
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    keep_at = args.steps - 1 if (args.dump_outputs and rank == 0) else -1
     for i in range(args.steps):
-        step(i % rec_every == 0)
+        step(i % rec_every == 0, i == keep_at)
     torch.cuda.synchronize()
     if grouped:
         dist.barrier()
@@ -690,6 +757,11 @@ def main():
         if grouped:
             dist.destroy_process_group()
         return
+    dumped = None
+    if kept:
+        note(f"writing the last step's outputs to {args.dump_outputs}")
+        dumped = dump_outputs(args.dump_outputs, kept)
+        kept.clear()
 
     frames = (1 if args.slabs else world) * B * args.steps
     fps = frames / el
@@ -704,7 +776,7 @@ def main():
     tap_bytes = 2 if (hm_planar.element_size() == 2 and J <= 16) else 4
 
     extra = {}
-    if rank == 0:
+    if rank == 0 and args.full:
         # measured copy bandwidth: fvp_copy_f4 (float4 streaming copy, 1 GiB each
         # way, csrc/fvp_copy.hip) on this stream; and the one-frame latency of
         # the step; both outside the timed region
@@ -821,7 +893,7 @@ def main():
             extra["latency_b1_abi_ms"] = float(np.median(lat))
 
     ceiling = None
-    if rank == 0:
+    if rank == 0 and args.full:  # (the ceiling needs the measured copy rate)
         ceiling = tap_floor_ceiling(Xs * Y * Z, V, J, Hd, Wd, hm_planar.element_size(),
                                     args.heatmap_layout == "planar", extra.get("copy_gbs"), per_frame)
         if world > 1:
@@ -871,7 +943,10 @@ def main():
             "cpu_baseline": cpu,
             "execution": "hipGraph replay of the GPU-local step" if args.graph == "on" else "eager",
             "cache_build": cache_ms,
+            "full": args.full,
         }
+        if dumped is not None:
+            line["outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if "channels_last" in extra:
             line["roofline"]["channels_last_input"] = extra["channels_last"]
         if args.heatmap_layout != "planar":

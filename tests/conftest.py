@@ -16,9 +16,10 @@ def pytest_configure(config):
 
 
 def golden(name):
-    import numpy as np
+    """tests/golden/<name> (and its .partN.npz files, where it is stored in parts)."""
+    from digest_cases import load_golden
 
-    return np.load(os.path.join(GOLDEN, name))
+    return load_golden(os.path.join(GOLDEN, name))
 
 
 @pytest.fixture(scope="session")

@@ -237,3 +237,48 @@ def test_traffic_split_per_kernel(tmp_path):
     k = 1024.0 / 2
     assert t["layout"] == (2 * 100 + 50) * k and t["gather"] == (300 + 20) * k
     assert t["traffic"] == (2 * 100 + 50 + 300 + 20) * k and t["traffic_upper"] == (2 * 100 + 50 + 600 + 20) * k
+
+
+def test_secondary_measurements_need_full():
+    """A plain run times the steps only: the traffic counters and the CPU baseline
+    are off unless --full is given, and asking for either without it is an error."""
+    _paths()
+    import bench
+
+    plain = bench.parse(["--gpus", "1", "--steps", "5", "--warmup", "1"])
+    assert (plain.full, plain.traffic, plain.cpu_baseline, plain.dump_outputs) == (False, "off", "off", None)
+    assert plain.steps == 5 and plain.warmup == 1
+    full = bench.parse(["--full"])
+    assert (full.full, full.traffic, full.cpu_baseline) == (True, "auto", "on")
+    quiet = bench.parse(["--full", "--traffic", "off", "--cpu-baseline", "off"])
+    assert (quiet.traffic, quiet.cpu_baseline) == ("off", "off")
+    bench.parse(["--traffic", "off", "--cpu-baseline", "off"])  # still accepted on a plain run
+    for argv in (["--traffic", "auto"], ["--cpu-baseline", "on"]):
+        with pytest.raises(SystemExit):
+            bench.parse(argv)
+
+
+def test_dump_outputs_writes_float_arrays_and_a_fixed_sample(tmp_path):
+    """bench.dump_outputs: small arrays whole (float32; int64 indices as float64,
+    exact), an array above the per-array limit as the same seeded sample of its
+    elements on every call."""
+    _paths()
+    import bench
+
+    g = torch.Generator().manual_seed(3)
+    n_big = bench.DUMP_ARRAY_BYTES // 4 + 1000
+    outs = {"vals": torch.rand((4, 10), generator=g),
+            "flat": torch.randint(0, 2 ** 40, (4, 10), generator=g),
+            "cube": torch.rand((n_big,), generator=g).view(2, -1)[:, :].t()}  # a non-contiguous view
+    info = bench.dump_outputs(str(tmp_path / "a"), outs)
+    bench.dump_outputs(str(tmp_path / "b"), outs)
+    got = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in outs}
+    assert got["vals"].dtype == np.float32 and np.array_equal(got["vals"], outs["vals"].numpy())
+    assert got["flat"].dtype == np.float64 and np.array_equal(got["flat"].astype(np.int64), outs["flat"].numpy())
+    assert info["vals"] == {"shape": [4, 10], "dtype": "float32", "sampled": False}
+    assert info["cube"]["sampled"] and got["cube"].nbytes == bench.DUMP_ARRAY_BYTES
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED).integers(0, n_big, bench.DUMP_ARRAY_BYTES // 4))
+    assert np.array_equal(got["cube"], outs["cube"].contiguous().view(-1).numpy()[idx])
+    for k in outs:
+        assert np.array_equal(got[k], np.load(tmp_path / "b" / f"{k}.npy"))
+    assert sum(a.nbytes for a in got.values()) <= 64_000_000

@@ -6,7 +6,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 run() {  # tag args... (STEPS / WARMUP: per-call overrides)
   local tag=$1; shift
-  timeout -k 10 300 python bench.py "$@" --steps ${STEPS:-10} --warmup ${WARMUP:-2} --traffic ${TRAFFIC:-off} \
+  timeout -k 10 300 python bench.py --full "$@" --steps ${STEPS:-10} --warmup ${WARMUP:-2} --traffic ${TRAFFIC:-off} \
     --cpu-baseline ${CPU:-off} > gpurun_out/all_$tag.log 2>&1
   local rc=$?; echo "$tag rc=$rc"; if [ $rc -ge 124 ]; then exit $rc; fi
 }

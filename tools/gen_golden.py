@@ -253,8 +253,11 @@ def main():
             d["u_cube_sub"] = cu.numpy().reshape(uniform_batch, J, N)[:, :, sub]
             d["u_xy"] = torch.max(cu, dim=4)[0].numpy()
             d["u_cube_sum"] = cu.numpy().astype(np.float64).sum(axis=(2, 3, 4))
-        np.savez_compressed(os.path.join(OUT, f"{name}.npz"), **d)
-        print("wrote", name, {k: v.shape for k, v in d.items()})
+        sys.path.insert(0, os.path.join(REPO, "tests"))
+        import digest_cases as dc
+
+        parts = dc.save_golden(os.path.join(OUT, f"{name}.npz"), d)  # (in parts of at most 1 MiB)
+        print("wrote", name, [os.path.basename(p) for p in parts], {k: v.shape for k, v in d.items()})
 
     if only is None or "whole" in only:
         whole_case("whole_c1", "c1", batch=2, uniform_batch=1, full=True)

@@ -34,7 +34,7 @@ for step in "$@"; do
     smoke) timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || fail smoke $O/smoke.log
            tail -1 $O/smoke.log ;;
     bench) rm -rf gpurun_out/bench_pmc
-           timeout -k 10 600 python bench.py $BENCH_ARGS > $O/bench.json 2> $O/bench.err || fail bench $O/bench.err
+           timeout -k 10 600 python bench.py --full $BENCH_ARGS > $O/bench.json 2> $O/bench.err || fail bench $O/bench.err
            if [ -d gpurun_out/bench_pmc ]; then mkdir -p $O/bench_pmc && cp -r gpurun_out/bench_pmc/. $O/bench_pmc/; fi
            cut -c1-400 $O/bench.json ;;
     prof)  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 bench.py --traffic off --cpu-baseline off $BENCH_ARGS > $O/prof.log 2>&1 || fail prof $O/prof.log
@@ -47,7 +47,7 @@ for step in "$@"; do
            cut -c1-300 $O/jln.json ;;
     all)   for wl in c1 c2 c3 c4 c5; do
              tr=off; case $wl in c4|c5) tr=auto;; esac  # (C4 / C5: the FETCH / WRITE counters too)
-             timeout -k 10 600 python bench.py --workload $wl --steps 10 --warmup 2 --traffic $tr --cpu-baseline on > $O/all_$wl.json 2> $O/all_$wl.err || fail all_$wl $O/all_$wl.err
+             timeout -k 10 600 python bench.py --full --workload $wl --steps 10 --warmup 2 --traffic $tr --cpu-baseline on > $O/all_$wl.json 2> $O/all_$wl.err || fail all_$wl $O/all_$wl.err
              echo "$wl: $(cut -c1-200 $O/all_$wl.json)"
            done
            for wb in c4:32 c5:32; do
@@ -63,7 +63,7 @@ for step in "$@"; do
            cut -c1-400 $O/bench_gloo2.json ;;
     ab)    for rep in $(seq 1 ${REPEAT:-2}); do
              for lib in $AB_LIBS; do
-               FVP_LIB=ab_libs/$lib.so timeout -k 10 300 python bench.py --traffic off --cpu-baseline off $BENCH_ARGS > $O/ab_${lib}_$rep.json 2> $O/ab_${lib}_$rep.err || fail ab_$lib $O/ab_${lib}_$rep.err
+               FVP_LIB=ab_libs/$lib.so timeout -k 10 300 python bench.py --full --traffic off --cpu-baseline off $BENCH_ARGS > $O/ab_${lib}_$rep.json 2> $O/ab_${lib}_$rep.err || fail ab_$lib $O/ab_${lib}_$rep.err
                echo "$lib $rep: $(python3 -c "import json,sys; b=json.loads(open(sys.argv[1]).readlines()[-1]); r=b['roofline']; print(b['value'], r['kernel_ms'], r['frac'], r.get('channels_last_input',{}).get('frac'))" $O/ab_${lib}_$rep.json)"
                if [ "$rep" = 1 ]; then
                  FVP_LIB=ab_libs/$lib.so timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/abprof_$lib -o run -- python3 bench.py --traffic off --cpu-baseline off $BENCH_ARGS > $O/abprof_$lib.log 2>&1 || fail abprof_$lib $O/abprof_$lib.log
