@@ -124,6 +124,8 @@ SIGNATURES = {
                           c_void_p, ctypes.c_longlong, ctypes.c_longlong, c_int, c_void_p],
     "fvp_up2_head_nchw": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                           c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p],
+    "fvp_render_keypoints": [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                             ctypes.c_double, ctypes.c_double, ctypes.c_double, c_int, c_void_p, c_void_p],
 }
 
 ABI_VERSION = 22

@@ -126,3 +126,89 @@ def share_channels_last(heatmaps) -> ChannelsLastHeatmaps | None:
     cl = to_channels_last(heatmaps)
     attach(heatmaps, cl, shared=True)
     return cl
+
+
+def pack_keypoints(all_preds, max_people: int | None = None):
+    """One frame's 2-D detections as the reference dataset holds them -- a list
+    over views of lists of ``[J, >= 2]`` arrays (x, y in image pixels after the
+    resize transform; a score column is ignored, as generate_input_heatmap
+    ignores it) -- as padded host tensors for :func:`render_keypoints`:
+    ``joints`` [V, P, J, 2] fp64 and ``count`` [V] int32, with P =
+    ``max_people`` or the largest view (at least 1).  Padded rows are zero and
+    never read.  Batches are stacked by the caller (``torch.stack``)."""
+    import numpy as np
+
+    views = [[np.asarray(p, dtype=np.float64) for p in view] for view in all_preds]
+    people = [p for view in views for p in view]
+    if not views:
+        raise _lib.FvpError("fvp: pack_keypoints: no views")
+    for p in people:
+        if p.ndim != 2 or p.shape[1] < 2 or p.shape[0] != people[0].shape[0]:
+            raise _lib.FvpError(f"fvp: pack_keypoints: each person is [J, >= 2] with one J, got {p.shape}")
+    most = max(len(view) for view in views)
+    P = max(most, 1) if max_people is None else int(max_people)
+    if most > P:
+        raise _lib.FvpError(f"fvp: pack_keypoints: a view holds {most} people, max_people = {P}")
+    if not people:
+        raise _lib.FvpError("fvp: pack_keypoints: no person in any view (the joint count is unknown)")
+    J = people[0].shape[0]
+    joints = np.zeros((len(views), P, J, 2), dtype=np.float64)
+    for v, view in enumerate(views):
+        for n, p in enumerate(view):
+            joints[v, n] = p[:, :2]
+    count = np.array([len(view) for view in views], dtype=np.int32)
+    return torch.from_numpy(joints), torch.from_numpy(count)
+
+
+def render_keypoints(joints: torch.Tensor, count: torch.Tensor, vis: torch.Tensor | None = None, *, image_size,
+                     heatmap_size, sigma: float) -> ChannelsLastHeatmaps:
+    """Input heatmaps painted from 2-D keypoints on the device, channels-last,
+    in one launch (fvp_render_keypoints): JointsDataset.generate_input_heatmap
+    (lib/dataset/JointsDataset.py:368-447) with ``data_augmentation = False``,
+    quirks included -- the ``TEST_HEATMAP_SRC: 'pred'`` input of Shelf and
+    Campus -- without the numpy painter, the planar host-to-device copy and
+    the layout pass.  The result feeds ``ProjectLayer`` directly, or as
+    ``.planar()`` through the reference's tensor-typed interfaces.
+
+    joints  [B, V, P, J, 2] fp64 or fp32 on a HIP device: image pixels after the
+            dataset's resize transform (what the reference hands to the painter)
+    count   [B, V] int32: people of each view (rows at or beyond it are never read)
+    vis     [B, V, P, J] uint8 or bool, optional: 0 = joint not painted
+    image_size, heatmap_size  (W, H) as NETWORK.IMAGE_SIZE / HEATMAP_SIZE;  sigma: NETWORK.SIGMA
+
+    A person with a non-finite coordinate is skipped (the reference raises).
+    Out of scope: the ``'gt'`` source (3-D joints projected through the cameras
+    first: project on the host and call this with ``vis``) and the
+    training-time random augmentation."""
+    from . import ops
+
+    if not isinstance(joints, torch.Tensor) or joints.dim() != 5 or joints.shape[4] != 2 \
+            or joints.dtype not in (torch.float32, torch.float64):
+        raise _lib.FvpError(f"fvp: render_keypoints takes joints fp64 / fp32 [B,V,P,J,2], got "
+                            f"{tuple(joints.shape)} {joints.dtype}")
+    B, V, P, J, _ = joints.shape
+    if J > 32 or P > 32 or J < 1 or P < 1:
+        raise _lib.FvpError(f"fvp: render_keypoints: {P} people x {J} joints (1..32 each)")
+    if not isinstance(count, torch.Tensor) or tuple(count.shape) != (B, V) or count.dtype != torch.int32:
+        raise _lib.FvpError(f"fvp: render_keypoints takes count int32 [B,V] = {(B, V)}, got "
+                            f"{tuple(count.shape)} {count.dtype}")
+    if vis is not None:
+        if tuple(vis.shape) != (B, V, P, J) or vis.dtype not in (torch.uint8, torch.bool):
+            raise _lib.FvpError(f"fvp: render_keypoints takes vis uint8 / bool [B,V,P,J] = {(B, V, P, J)}, got "
+                                f"{tuple(vis.shape)} {vis.dtype}")
+        if vis.dtype == torch.bool:
+            vis = vis.view(torch.uint8)
+    for name, t in (("joints", joints), ("count", count), ("vis", vis)):
+        if t is None:
+            continue
+        if t.device.type != "cuda" or t.device != joints.device:
+            raise _lib.FvpError(f"fvp: render_keypoints: {name} must be on a HIP device (one for all operands), got "
+                                f"{t.device}")
+        if not t.is_contiguous():
+            raise _lib.FvpError(f"fvp: render_keypoints: {name} must be contiguous")
+    (img_w, img_h), (W, H) = image_size, heatmap_size
+    if int(W) != W or int(H) != H or W < 1 or H < 1 or not (img_w > 0 and img_h > 0 and sigma > 0):
+        raise _lib.FvpError(f"fvp: render_keypoints: image {image_size}, heatmap {heatmap_size}, sigma {sigma}")
+    ops.forward_only(joints)
+    t = ops.render_keypoints(joints, count, vis, float(img_w), float(img_h), int(H), int(W), float(sigma))
+    return ChannelsLastHeatmaps(t, J)

@@ -546,6 +546,38 @@ int fvp_weight_net(const float *features, int Nimg, int H, int W, const float *c
 int fvp_nchw_to_nhwc(const float *in, int N, int C, int H, int W, int Cp, float *out, void *stream);
 int fvp_nhwc_to_nchw(const float *in, int N, int C, int H, int W, int Cp, float *out, void *stream);
 
+/* Input heatmaps painted from 2-D keypoints, written channels-last in one
+ * launch: what JointsDataset.generate_input_heatmap (lib/dataset/JointsDataset.py:
+ * 368-447, with compute_human_scale :265-279) paints per view in numpy with
+ * data_augmentation = False -- the TEST_HEATMAP_SRC 'pred' heatmaps of Shelf and
+ * Campus -- in the layout fvp_voxelize_cl / fvp_person_planes_cl read in place.
+ * Per person (all J joints, visibility plays no part), in fp64 in the
+ * reference's operation order:
+ *   q = joint / (image_size / heatmap_size);  ext = max(max_y - min_y, max_x - min_x) of q
+ *   cur_sigma = sigma * sqrt(2 * clip(ext^2, 96^2 / 4, 4 * 96^2) / 96^2);  tmp = 3 * cur_sigma
+ * per visible joint, with C truncation toward zero as Python's int():
+ *   mu = (int)q;  ul = (int)(mu - tmp);  br = (int)(mu + tmp + 1)
+ *   skipped iff ul.x >= W || ul.y >= H || br.x < 0 || br.y < 0
+ *   pixel (x, y) in [max(0, ul), min(br, (W, H))) and within ceil(2 tmp + 1) of ul gets
+ *   exp(-(dx^2 + dy^2) / (2 cur_sigma^2)),  (dx, dy) = (x, y) - (ul + floor((2 tmp + 1) / 2))
+ * (the Gaussian sits on the centre of its patch, which is not always mu), and a
+ * channel's pixel is the max over the frame-view's people.  The value is fp32:
+ * expf of the exact integer dx^2 + dy^2 times (float)(1 / (2 cur_sigma^2)).
+ * One deviation: a person with a non-finite coordinate is skipped (the
+ * reference raises from int(nan)); coordinates beyond +-2^30 heatmap pixels are
+ * pinned there.
+ *   joints  device [B][V][P][J][2] image pixels (after the dataset's resize
+ *           transform), fp64 (joints_f64 != 0) or fp32 (widened on load)
+ *   count   device int32 [B][V]: people of that view, 0 <= count <= P; rows at or
+ *           beyond count are never read
+ *   vis     device uint8 [B][V][P][J] or NULL (all visible)
+ *   out_cl  device [B][V][H][W][Cp] fp32, Cp % 16 == 0, J <= Cp <= 32: every element
+ *           is written (channels J..Cp-1 and uncovered pixels 0.0f); no workspace
+ * J <= 32, P <= 32; image_w, image_h, sigma > 0. */
+int fvp_render_keypoints(const void *joints, int joints_f64, const int *count, const unsigned char *vis, int B,
+                         int V, int P, int J, int H, int W, double image_w, double image_h, double sigma, int Cp,
+                         float *out_cl, void *stream);
+
 /* Roofline calibration (not on the product path): a float4 streaming copy of
  * `bytes` (multiple of 16) from src to dst; bench.py reports the op's HBM
  * rate as a fraction of this kernel's measured rate besides the nominal peak. */
