@@ -43,7 +43,8 @@ __device__ __forceinline__ float block_reduce_sum(float v, float *red) {
 
 // feat [3][P][J][S2], grids [3][S2][2], offset [P][3] (may be NULL)
 // pose [3][P][J][2], maxprob [3][P][J]
-// The row is read once: S2 <= 256*4*RV values stay in registers (float4 loads).
+// The row is read once: S2 <= 256*4*RV values stay in registers (float4 loads where
+// the rows are 16-byte aligned).  grids is read as float2: 8-byte aligned.
 template <int RV>
 __global__ __launch_bounds__(256) void softargmax_kernel(const float *__restrict__ feat,
                                                          const float *__restrict__ grids,
@@ -56,7 +57,9 @@ __global__ __launch_bounds__(256) void softargmax_kernel(const float *__restrict
     const int p = (row / J) % P;
     const float *__restrict__ x = feat + (size_t)row * S2;
     const float *__restrict__ g = grids + (size_t)plane * S2 * 2;
-    const bool vec = (S2 & 3) == 0;
+    // float4 loads need every row 16-byte aligned: S2 % 4 == 0 and an aligned base (a contiguous
+    // view may start anywhere in its buffer); otherwise the scalar loads, same cells per thread
+    const bool vec = (S2 & 3) == 0 && (reinterpret_cast<uintptr_t>(feat) & 15) == 0;
     float y[RV][4];
     float m = -INFINITY;
 #pragma unroll
@@ -340,6 +343,7 @@ extern "C" int fvp_soft_argmax(const float *features, int P, int J, int S2, cons
     if (!features || !center_grid || !pose || !maxprob) return FVP_ERR_NULL;
     if (P < 0 || J <= 0 || S2 <= 0) return FVP_ERR_SHAPE;
     if ((long long)3 * P * J > 0x7fffffffLL) return FVP_ERR_SHAPE;
+    if (reinterpret_cast<uintptr_t>(center_grid) & 7) return FVP_ERR_SHAPE;  // read as float2
     const dim3 grid((unsigned)(3 * P * J));
     if (S2 > 256 * 4 * 8)  // beyond 8192 cells per plane (64x64 = 4096): two passes over the row
         hipLaunchKernelGGL(fvp::softargmax_stream_kernel, grid, dim3(256), 0, (hipStream_t)stream, features,

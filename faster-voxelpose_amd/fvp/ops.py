@@ -694,6 +694,8 @@ def soft_argmax(features: torch.Tensor, center_grid: torch.Tensor, offset: Optio
     """features [3,P,J,S,S] (or [3,P,J,S*S,1]) -> (pose [3,P,J,2] (+offset), maxprob [3,P,J])."""
     f = _dev_f32(features, "features")
     g = _dev_f32(center_grid, "center_grid")
+    if g.data_ptr() % 8:  # the kernel reads (x, y) pairs; a view may start mid-pair
+        g = g.clone()
     P, J = f.shape[1], f.shape[2]
     S2 = f[0, 0, 0].numel() if P > 0 else g.shape[1]
     if g.numel() != 3 * S2 * 2:

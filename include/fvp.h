@@ -287,7 +287,11 @@ int fvp_max_planes(const float *cubes, int P, int J, int S, float *planes, void 
  * and the offset additions of JointLocalizationNet.forward (:170-174).
  *   features    device [3][P][J][S2] (P2PNet output, chunked and stacked by plane)
  *   center_grid device [3][S2][2] (project_individual.ProjectLayer.center_grid)
- *   offset      device [P][3] or NULL;  pose [3][P][J][2], maxprob [3][P][J] outputs */
+ *   offset      device [P][3] or NULL;  pose [3][P][J][2], maxprob [3][P][J] outputs
+ * Alignment: features needs only its 4-byte element alignment (16-byte loads are used
+ * when features is 16-byte aligned and S2 % 4 == 0, scalar loads otherwise, with the
+ * same result bit for bit); center_grid is read as (x, y) pairs and must be 8-byte
+ * aligned, else FVP_ERR_SHAPE. */
 int fvp_soft_argmax(const float *features, int P, int J, int S2, const float *center_grid,
                     const float *offset, float beta, float *pose, float *maxprob, void *stream);
 

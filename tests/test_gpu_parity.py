@@ -617,7 +617,15 @@ def test_soft_argmax_long_rows(gpu_device):
     ref_pose = O.add_offsets(ref_pose, off.numpy())
     y = 100.0 * feat.numpy().reshape(3, P, J, -1).astype(np.float64)
     ref_mp = 1.0 / np.exp(y - y.max(axis=3, keepdims=True)).sum(axis=3)  # max of the softmax
+    # the derived per-row fp32 bound of tests/jln_ref.py (0.03 mm on these inputs) on top of 0.05 mm
+    import jln_ref
+
+    ref = jln_ref.soft_argmax_ref(feat.numpy(), grid.numpy(), off.numpy(), 100.0)
+    assert np.array_equal(ref["pose"], ref_pose)
     assert np.abs(pose.cpu().numpy() - ref_pose).max() <= 0.05
+    pr, mr = jln_ref.ratios(pose.cpu().numpy(), maxprob.cpu().numpy(), ref)
+    print(f"long rows: pose error {pr:.4f} x bound (<= {ref['bound'].max():.5f} mm), maxprob {mr:.4f} x allowance")
+    assert pr <= 1.0 and mr <= 1.0
     assert np.abs(maxprob.cpu().numpy() - ref_mp).max() <= 1e-5
 
 
