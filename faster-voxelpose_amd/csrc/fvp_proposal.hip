@@ -8,9 +8,10 @@
 // deterministic.  Indices decode as get_index2D does, dividing by
 // shape[1] == X (proposal.py:27-29,75).
 //
-// nms_select_kernel (K <= 16, X*Y <= 32640): one 1024-thread block per frame,
-// the elements' 64-bit order keys in registers; a threshold from the wave
-// maxima bounds the candidates, which are compacted and ranked (below).
+// nms_select_kernel (K <= 16, X*Y <= 32512: nms_any's sel_lds <= 159 KiB):
+// one 1024-thread block per frame, the elements' 64-bit order keys in
+// registers; a threshold from the maxima of the 16-lane rows bounds the
+// candidates, which are compacted and ranked (below).
 // nms_topk_kernel (K > 16): one 256-thread block per frame, the masked map in
 // LDS, K block-wide arg-max rounds over a taken bitmap.
 #include "fvp_device.h"
@@ -231,7 +232,13 @@ __device__ __forceinline__ void write_winner(int b, int K, int slot, int idx, fl
 //      is its output slot when < K.
 // A list longer than kSelCap (only for adversarial value layouts) falls back
 // to K block-wide extraction rounds of the largest key below the previous
-// winner (no taken bitmap: keys are unique).
+// winner (no taken bitmap: keys are unique; round 0 takes any key, so that a
+// NaN at flat index 0, whose key is ~0ull, is picked).  At most K - 1 rows have
+// a maximum above t and a row owns 16 elements per 1024, so
+// C <= (K - 1) * 16 * ceil(M / 1024) + 1: more than 4096 needs ceil(M / 1024)
+// >= 18, which only nms_select_kernel<32, false> sees (the strips stop at
+// M = 16384), for 17408 < M <= 32512 and K >= 9.  tests/test_gpu_nms_select.py
+// runs the fallback (its candidate counts from tests/nms_select_model.py).
 //
 // STRIP (Y <= 1024, es = ceil(X / (1024 / Y)) <= E <= 16): the masked map is
 // computed by column strips -- thread (xb, y) owns (xb*es .. xb*es + es - 1, y),
@@ -386,13 +393,14 @@ __global__ __launch_bounds__(kSelThreads) void nms_select_kernel(const float *__
                 write_winner(b, K, rank, idx, (STRIP ? map[idx] : masked_value(map, idx, X, Y, rY)), X, vals, flat, xy, widx);
             }
         }
-    } else {  // K rounds, each the largest key below the previous winner
-        unsigned long long prev = ~0ull;
+    } else {  // K rounds: the largest key of all, then each time the largest below the previous winner
+        unsigned long long prev = 0;
         for (int r = 0; r < K; ++r) {
             unsigned long long mine = 0;
+            // round 0 takes any key: a NaN at flat index 0 has the key ~0ull, which no bound lies above
 #pragma unroll
             for (int i = 0; i < E; ++i)
-                if (key[i] < prev && key[i] > mine) mine = key[i];
+                if ((r == 0 || key[i] < prev) && key[i] > mine) mine = key[i];
             const unsigned long long wm = wave_max_key(mine);
             if (lane == 0) wmax[wave] = wm;
             __syncthreads();

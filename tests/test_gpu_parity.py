@@ -742,8 +742,8 @@ def test_nms_topk_both_paths_vs_oracle(gpu_device, K):
     got = v.cpu().numpy()
     assert np.array_equal(np.isnan(got), np.isnan(ov))
     assert np.array_equal(np.nan_to_num(got, nan=7.0), np.nan_to_num(ov, nan=7.0))
-    assert np.array_equal(fl.cpu().numpy()[1:], ofl[1:])  # frame 0 holds a NaN (ordering checked above)
-    assert np.array_equal(xy.cpu().numpy()[1:], oxy[1:])
+    assert np.array_equal(fl.cpu().numpy(), ofl)  # frame 0, which holds the NaN, included
+    assert np.array_equal(xy.cpu().numpy(), oxy)
 
 
 @pytest.mark.parametrize("kind", ["zeros", "nan", "negative", "tiny", "big_noise", "big_smooth", "row", "ragged",
