@@ -201,7 +201,7 @@ __global__ __launch_bounds__(kC2CThreads) void c2c_net_kernel(const float *__res
                 if (lo >= Lout) continue;
                 float v = acc[j] * sv + bv;
                 if (rpre) v = v + rpre[row + lo];
-                if (op.relu) v = fmaxf(v, 0.0f);
+                if (op.relu) v = reluf(v);
                 if (rpost) v = v + rpost[row + lo];
                 out[row + lo] = v;
             }

@@ -265,7 +265,7 @@ __device__ __forceinline__ void epilogue_write(const ConvArgs &a, const RowM &ro
         }
         if (a.relu) {
 #pragma unroll
-            for (int k = 0; k < 8; ++k) v[k] = fmaxf(v[k], 0.0f);
+            for (int k = 0; k < 8; ++k) v[k] = reluf(v[k]);
         }
         if (a.res_post) {
             float r8[8];
@@ -458,7 +458,7 @@ __global__ __launch_bounds__(256) void conv_splitk_reduce(ConvArgs a, int M, int
     const size_t off = conv_out_offset(a, m, n, g, co);
     v = v * a.scale[co] + a.shift[co];
     if (a.res_pre) v = v + a.res_pre[off];
-    if (a.relu) v = fmaxf(v, 0.0f);
+    if (a.relu) v = reluf(v);
     if (a.res_post) v = v + a.res_post[off];
     a.out[off] = v;
 }
@@ -1077,6 +1077,10 @@ __global__ __launch_bounds__(256, 2) void conv_stem7_bf16_kernel(const float *__
                 for (int i = 0; i < 2; ++i) {
                     const int oyl = wave * 2 + i;
                     fa[i] = *reinterpret_cast<const bf16x8 *>(halo + ((2 * oyl + ky) * kStemHX + 2 * px + kx) * 4);
+                    if (s == 1 && h == 1) {  // kx + 1 = 7, the zero tap: no image data (Inf x 0 would be NaN)
+#pragma unroll
+                        for (int c = 4; c < 8; ++c) fa[i][c] = (__bf16)0.0f;
+                    }
                 }
 #pragma unroll
                 for (int j = 0; j < 2; ++j)
@@ -1099,10 +1103,10 @@ __global__ __launch_bounds__(256, 2) void conv_stem7_bf16_kernel(const float *__
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
                     bf16x4 o;
-                    o[0] = (__bf16)fmaxf(acc[i][j][4 * q + 0] * sc.x + sh.x, 0.0f);
-                    o[1] = (__bf16)fmaxf(acc[i][j][4 * q + 1] * sc.y + sh.y, 0.0f);
-                    o[2] = (__bf16)fmaxf(acc[i][j][4 * q + 2] * sc.z + sh.z, 0.0f);
-                    o[3] = (__bf16)fmaxf(acc[i][j][4 * q + 3] * sc.w + sh.w, 0.0f);
+                    o[0] = (__bf16)reluf(acc[i][j][4 * q + 0] * sc.x + sh.x);
+                    o[1] = (__bf16)reluf(acc[i][j][4 * q + 1] * sc.y + sh.y);
+                    o[2] = (__bf16)reluf(acc[i][j][4 * q + 2] * sc.z + sh.z);
+                    o[3] = (__bf16)reluf(acc[i][j][4 * q + 3] * sc.w + sh.w);
                     *reinterpret_cast<bf16x4 *>(st + ((wave * 2 + i) * kStemTW + px) * kStemOP + co) = o;
                 }
             }
@@ -1234,7 +1238,7 @@ __global__ __launch_bounds__(256, 2) void conv_stem7_f32_kernel(const float *__r
                 for (int c = 0; c < 4; ++c) {
                     f32x4 v;
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) v[k] = fmaxf(acc[c][p][k] * sc[c][k] + sh[c][k], 0.0f);
+                    for (int k = 0; k < 4; ++k) v[k] = reluf(acc[c][p][k] * sc[c][k] + sh[c][k]);
                     *reinterpret_cast<f32x4 *>(o + 16 * c) = v;
                 }
             }
@@ -1250,7 +1254,9 @@ __global__ __launch_bounds__(256, 2) void conv_stem7_f32_kernel(const float *__r
 // before it).  A block owns an 8 x 32 output tile: the 14 x 38 input halo of
 // the C planes goes to LDS once as bf16 [row][x][16 channels] (48-B pixel
 // pitch: conflict-free fragment reads), the weights [16][50 taps][16] (tap 49
-// and channels >= C zero) beside it.  v_mfma_f32_16x16x32_bf16 with the
+// and channels >= C zero) beside it.  Tap 49 reads one zero pixel kept after
+// the halo, never image data: Inf x its zero weight would be NaN.
+// v_mfma_f32_16x16x32_bf16 with the
 // weights as the A operand: K step = 2 taps x 16 channels, a lane's 8 k values
 // = 8 channels of one tap (16 contiguous bytes), and the output comes out with
 // lane -> pixel, 4 registers -> 4 consecutive channels.
@@ -1263,7 +1269,8 @@ __global__ __launch_bounds__(256) void conv_front7_bf16_kernel(const float *__re
                                                                const float *__restrict__ scale,
                                                                const float *__restrict__ shift,
                                                                __bf16 *__restrict__ out) {
-    constexpr int HALO_B = kFrHR * kFrHX * kFrPB, W_B = 16 * kFrWP * 2, OUT_B = kFrTH * kFrTW * 16 * 2;
+    constexpr int kZeroPx = kFrHR * kFrHX;  // the pad tap's pixel: zeros
+    constexpr int HALO_B = (kZeroPx + 1) * kFrPB, W_B = 16 * kFrWP * 2, OUT_B = kFrTH * kFrTW * 16 * 2;
     __shared__ __attribute__((aligned(16))) unsigned char smem[HALO_B + W_B + OUT_B];
     unsigned char *halo = smem;
     __bf16 *wl = reinterpret_cast<__bf16 *>(smem + HALO_B);
@@ -1288,6 +1295,7 @@ __global__ __launch_bounds__(256) void conv_front7_bf16_kernel(const float *__re
         *reinterpret_cast<bf16x8 *>(halo + e * kFrPB) = h0;
         *reinterpret_cast<bf16x8 *>(halo + e * kFrPB + 16) = h1;
     }
+    if (t < kFrPB / 16) *reinterpret_cast<uint4 *>(halo + kZeroPx * kFrPB + 16 * t) = uint4{0u, 0u, 0u, 0u};
     for (int e = t; e < 16 * 100; e += 256) {  // weights: 16 rows x 100 pieces of 8
         const int co = e / 100, q = e - (e / 100) * 100;
         *reinterpret_cast<uint4 *>(wl + co * kFrWP + q * 8) = *reinterpret_cast<const uint4 *>(wpk + co * 800 + q * 8);
@@ -1303,12 +1311,11 @@ __global__ __launch_bounds__(256) void conv_front7_bf16_kernel(const float *__re
         const int tap = 2 * s + (g >> 1), half = g & 1;  // this lane's tap (49: zero weights) and channel half
         const int ky = tap / 7, kx = tap - (tap / 7) * 7;
         const bf16x8 fw = *reinterpret_cast<const bf16x8 *>(wl + px * kFrWP + tap * 16 + half * 8);
-        const int tky = tap < 49 ? ky : 0, tkx = tap < 49 ? kx : 0;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int oyl = wave * 2 + (i >> 1), oxl = (i & 1) * 16 + px;
-            const bf16x8 fa = *reinterpret_cast<const bf16x8 *>(halo + ((oyl + tky) * kFrHX + oxl + tkx) * kFrPB +
-                                                                  half * 16);
+            const int hp = tap < 49 ? (oyl + ky) * kFrHX + oxl + kx : kZeroPx;
+            const bf16x8 fa = *reinterpret_cast<const bf16x8 *>(halo + hp * kFrPB + half * 16);
             acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw, fa, acc[i], 0, 0, 0);
         }
     }
@@ -1319,10 +1326,10 @@ __global__ __launch_bounds__(256) void conv_front7_bf16_kernel(const float *__re
     for (int i = 0; i < 4; ++i) {
         const int pix = (wave * 2 + (i >> 1)) * kFrTW + (i & 1) * 16 + px;
         bf16x4 o;
-        o[0] = (__bf16)fmaxf(acc[i][0] * sc.x + sh.x, 0.0f);
-        o[1] = (__bf16)fmaxf(acc[i][1] * sc.y + sh.y, 0.0f);
-        o[2] = (__bf16)fmaxf(acc[i][2] * sc.z + sh.z, 0.0f);
-        o[3] = (__bf16)fmaxf(acc[i][3] * sc.w + sh.w, 0.0f);
+        o[0] = (__bf16)reluf(acc[i][0] * sc.x + sh.x);
+        o[1] = (__bf16)reluf(acc[i][1] * sc.y + sh.y);
+        o[2] = (__bf16)reluf(acc[i][2] * sc.z + sh.z);
+        o[3] = (__bf16)reluf(acc[i][3] * sc.w + sh.w);
         *reinterpret_cast<bf16x4 *>(st + pix * 16 + 4 * g) = o;
     }
     __syncthreads();
@@ -1432,7 +1439,7 @@ __global__ __launch_bounds__(256, 2) void conv_front7_f32_kernel(const float *__
             if (oy < H && ox < W) {
                 f32x4 o;
 #pragma unroll
-                for (int k = 0; k < 4; ++k) o[k] = fmaxf(acc[i][k] * sc[k] + sh[k], 0.0f);
+                for (int k = 0; k < 4; ++k) o[k] = reluf(acc[i][k] * sc[k] + sh[k]);
                 *reinterpret_cast<f32x4 *>(out + (((size_t)n * H + oy) * W + ox) * 16 + 4 * g) = o;
             }
         }
@@ -1712,7 +1719,7 @@ __global__ __launch_bounds__(256) void conv1x1_nchw_kernel(const float *__restri
             for (int k = 0; k < 4; ++k) acc = __builtin_fmaf(xv[q][k], wv[k], acc);
         }
         float v = acc * ss[co] + ss[64 + co];
-        if (relu) v = fmaxf(v, 0.0f);
+        if (relu) v = reluf(v);
         o[(size_t)co * HW] = v;
     }
 }
@@ -1844,7 +1851,7 @@ __global__ __launch_bounds__(256) void up2_head_nchw_kernel(const float *__restr
                 const int px = 16 * mt + 4 * cm + r;
                 float *yp = yl + (64 * (cls >> 1) + 2 * px + (cls & 1)) * kUpY + (co >> 4) * 16 + (co & 3) * 4 +
                             ((co >> 2) & 3);
-                *yp = fmaxf(acc[i][r] * sc[i] + sh[i], 0.0f) + *yp;
+                *yp = reluf(acc[i][r] * sc[i] + sh[i]) + *yp;
             }
         }
         __syncthreads();  // (B2) y complete; x read

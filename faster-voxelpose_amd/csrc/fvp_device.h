@@ -65,6 +65,11 @@ __device__ __forceinline__ float clampf(float x, float lo, float hi) {
     return (x != x) ? x : fminf(fmaxf(x, lo), hi);
 }
 
+// torch.relu: NaN propagates (fmaxf(NaN, 0) is 0).  Equal (==) to fmaxf(v, 0) for every other v.
+__device__ __forceinline__ float reluf(float v) {
+    return v < 0.0f ? 0.0f : v;
+}
+
 // torch.max reduction: NaN propagates.
 __device__ __forceinline__ float nanmax(float a, float b) {
     return (b > a || b != b) ? b : a;

@@ -300,7 +300,7 @@ __global__ __launch_bounds__(256 * XS, XS == 1 ? 2 : 1) void conv_wino_kernel(Wi
                     float v = dx == 0 ? (f[dy][0] + f[dy][1]) + f[dy][2] : (f[dy][1] - f[dy][2]) - f[dy][3];
                     v = v * sc + sh;
                     if (rpre_p) v = v + rv[rr][q];
-                    if (a.relu) v = fmaxf(v, 0.0f);
+                    if (a.relu) v = reluf(v);
                     if (rpost_p) v = v + (rpre_p ? (ok ? rpost_p[off] : 0.0f) : rv[rr][q]);
                     pv[q] = v;
                     if (ok) a.out[off] = v;
@@ -478,7 +478,7 @@ __global__ __launch_bounds__(256, 2) void deconv_wino_kernel(WinoArgs a) {
                 float v = f[dy][dx] + f[dy][dx + 1];
                 v = v * sc + sh;
                 if (rpre_p) v = v + rpre_p[off];
-                if (a.relu) v = fmaxf(v, 0.0f);
+                if (a.relu) v = reluf(v);
                 if (rpost_p) v = v + rpost_p[off];
                 a.out[off] = v;
             }

@@ -328,6 +328,16 @@ int fvp_scatter_poses(const long long *idx, int P, int B, int K, int J, const fl
  *   out = act(conv(in, W) * scale + shift + res_pre) + res_post
  * with eval-mode BatchNorm and the conv bias folded into scale/shift, act =
  * ReLU when relu != 0.  Stride 1, zero padding (K-1)/2, odd KH/KW.
+ * Non-finite activations (every convolution entry point below, the Winograd,
+ * stem / front, 1x1-NCHW, fused-tail and one-launch 1-D kernels included)
+ * propagate as in torch: a NaN or Inf input element reaches exactly the real
+ * output channels of the windows that hold it and no other pixel or image; the
+ * ReLU keeps NaN (torch.relu, not fmaxf(v, 0)); zero padding taps and zero K
+ * rows read no image data, so an Inf never meets a zero weight there.  The
+ * Winograd kernels transform whole input patches: they may widen a NaN (and
+ * turn an Inf into NaN) within the tiles whose input patch holds the element,
+ * never past them.  Padded output channels (>= Cout) are unspecified after a
+ * non-finite input (Inf x their zero weights is NaN).
  * upsample2 == 1: ConvTranspose2d(k=2, s=2) as a 1x1 conv with 4*Cpo packed
  * outputs n = (dy*2+dx)*Cpo + co, scattered to the 2H x 2W output.
  * upsample2 == 2: ConvTranspose1d(k=2, s=2) (cnns_1d.py:96-123) on rows of
