@@ -383,6 +383,9 @@ __device__ __forceinline__ Taps4<PAIR> setup_taps(float gx, float gy, float sxs,
 
 inline int lanes_per_voxel(int J) { return J <= 4 ? 1 : J <= 8 ? 2 : J <= 16 ? 4 : 8; }
 
+// fp16 channels-last pixels: a lane's 16 B hold 8 joints (J <= 32 per slice).
+inline int lanes_per_voxel_h(int J) { return J <= 8 ? 1 : J <= 16 ? 2 : 4; }
+
 inline size_t cl_frame_bytes(int V, int J, int H, int W) {
     return (size_t)V * H * W * 4 * lanes_per_voxel(J) * sizeof(float);
 }
@@ -393,6 +396,32 @@ inline void launch_layout(const T *hm, int nb, int V, int J, int Jst, int H, int
     const long long threads = px * LPV;
     hipLaunchKernelGGL((heatmaps_to_cl_kernel<LPV, T, NF>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s,
                        hm, reinterpret_cast<float4 *>(cl), J, Jst, H * W, V, px);
+}
+
+// -- planar -> channels-last fp16 --------------------------------------------------
+// [N][C][H*W] fp32 or fp16 -> [N][H*W][Cp] fp16 (Cp % 8 == 0, channels C..Cp-1
+// zero): thread = (pixel, 8-channel group q) reads 8 planes at its pixel (the
+// lanes of a wave cover 64 / (Cp/8) consecutive pixels) and writes one 16-B
+// piece; a wave writes a contiguous 1 KiB run.  fp32 -> fp16 rounds to nearest
+// even (v_cvt_f16_f32), as Tensor.half().
+template <typename T>
+__global__ __launch_bounds__(256) void planar_to_cl_half_kernel(const T *__restrict__ in, uint4 *__restrict__ out,
+                                                                int C, int HW, int G, long long total_px) {
+    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long pxg = gid / G;
+    const int q = (int)(gid - pxg * G);
+    if (pxg >= total_px) return;
+    const long long n = pxg / HW;
+    const int pix = (int)(pxg - n * HW);
+    const T *__restrict__ src = in + (size_t)n * C * HW + pix;
+    unsigned h[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const int c = 8 * q + k;
+        const _Float16 v = c < C ? (_Float16)src[(size_t)c * HW] : (_Float16)0.0f;
+        h[k] = __builtin_bit_cast(unsigned short, v);
+    }
+    out[gid] = make_uint4(h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16));
 }
 
 }  // namespace fvp

@@ -145,8 +145,9 @@ struct PersonCoords {
 // fvp_device.h), before the division.  A group of LPV lanes shares the voxel
 // (lane q holds joints 4q..4q+3); `valid` false (outside the window or the
 // cube) gives 0.  Coordinates from the packed fine grid or projected on the fly.
-template <int LPV, bool OTF, bool CASC, int MODE>
-__device__ __forceinline__ void person_voxel_sum(float (&acc)[4], bool valid, int gx, int gy, int gz,
+// JPL = 8: fp16 channels-last pixels, lane q holds joints 8q..8q+7 (fvp_voxelize.hip).
+template <int LPV, bool OTF, bool CASC, int MODE, int JPL = 4>
+__device__ __forceinline__ void person_voxel_sum(float (&acc)[JPL], bool valid, int gx, int gy, int gz,
                                                  const __amdgpu_buffer_rsrc_t &grs, const float *lcam, const float *rt,
                                                  const PersonCoords &pc, const fvp_person_spec &s,
                                                  const char *__restrict__ frame_cl, unsigned img, unsigned qo, int q,
@@ -154,8 +155,10 @@ __device__ __forceinline__ void person_voxel_sum(float (&acc)[4], bool valid, in
                                                  unsigned pix_bytes) {
     constexpr int CPG = 2 * LPV;  // cameras per packed-grid load (2 per lane)
 #pragma unroll
-    for (int m = 0; m < 4; ++m) acc[m] = 0.0f;
-    float blk[4] = {0.f, 0.f, 0.f, 0.f};  // CASC: completed 16-camera blocks (fvp_device.h)
+    for (int m = 0; m < JPL; ++m) acc[m] = 0.0f;
+    float blk[JPL];  // CASC: completed 16-camera blocks (fvp_device.h)
+#pragma unroll
+    for (int m = 0; m < JPL; ++m) blk[m] = 0.0f;
     if (__builtin_amdgcn_ballot_w64(valid)) {
         const long long gn = valid ? ((long long)gx * s.fine[1] + gy) * s.fine[2] + gz : 0;
         float wxc = 0.f, wyc = 0.f, wzc = 0.f;  // OTF: fine voxel centre (compute_grid at fine resolution)
@@ -193,7 +196,7 @@ __device__ __forceinline__ void person_voxel_sum(float (&acc)[4], bool valid, in
                 if constexpr (CASC) {
                     if ((v & 15) == 0 && v > 0) {
 #pragma unroll
-                        for (int m = 0; m < 4; ++m) {
+                        for (int m = 0; m < JPL; ++m) {
                             blk[m] = blk[m] + acc[m];
                             acc[m] = 0.0f;
                         }
@@ -228,6 +231,15 @@ __device__ __forceinline__ void person_voxel_sum(float (&acc)[4], bool valid, in
                     tc = __builtin_amdgcn_raw_buffer_load_b128(rs, o[2] + qo, 0, 0);
                     td = __builtin_amdgcn_raw_buffer_load_b128(rs, o[3] + qo, 0, 0);
                 }
+                if constexpr (JPL == 8) {
+                    // word i of a piece = joints 8q+2i (low half), 8q+2i+1 (high half)
+                    static_for(std::make_integer_sequence<int, 8>{}, [&](auto mc) {
+                        constexpr int m = decltype(mc)::value, HI = m & 1, wd = m >> 1;
+                        const float t = fma_h<HI>(ta[wd], wt[0], -0.0f);
+                        acc[m] = acc[m] + fma_h<HI>(td[wd], wt[3], fma_h<HI>(tc[wd], wt[2], fma_h<HI>(tb[wd], wt[1], t)));
+                    });
+                    return;
+                }
 #pragma unroll
                 for (int m = 0; m < 4; ++m) {
                     const float fa = __builtin_bit_cast(float, (unsigned)ta[m]);
@@ -242,7 +254,7 @@ __device__ __forceinline__ void person_voxel_sum(float (&acc)[4], bool valid, in
     }
     // the sum's final levels (fvp_device.h): remainder + blocks, or + 0 (a -0 sum becomes +0)
 #pragma unroll
-    for (int m = 0; m < 4; ++m) acc[m] = acc[m] + (CASC ? blk[m] : 0.0f);
+    for (int m = 0; m < JPL; ++m) acc[m] = acc[m] + (CASC ? blk[m] : 0.0f);
 }
 
 // MODE (replay probe, tools/person_probe.hip; the product launches 0): 1 = no
@@ -251,19 +263,21 @@ __device__ __forceinline__ void person_voxel_sum(float (&acc)[4], bool valid, in
 // memory access), 4 = grid loads and tap setup only (no tap loads, no planes),
 // 5 / 6 = no xz / xy plane atomics or stores, 7 = xz atomics from even z lanes only,
 // 8 = plain stores instead of the xz atomics (timing only: wrong maxima).
-template <int LPV, bool OTF, bool CASC, int MODE = 0>
-__global__ __launch_bounds__(64 * LPV) void person_cl_kernel(const float *__restrict__ cl,
-                                                             const float *__restrict__ fgrid, PersonCoords pc,
-                                                             const float *__restrict__ props,
-                                                             const int32_t *__restrict__ frame_of, fvp_person_spec s,
-                                                             float *__restrict__ cubes, float *__restrict__ planes,
-                                                             float *__restrict__ offset, int P, int V, int J, int Jst,
-                                                             int H, int W, int xmap, int xsplit, int zsplit,
-                                                             unsigned pix_bytes, int xy_direct) {
+// JPL joints per lane: 4 (fp32 pixels) or 8 (fp16 pixels, JP = 8 * LPV joints per block).
+template <int LPV, bool OTF, bool CASC, int MODE, int JPL>
+__device__ __forceinline__ void person_cl_body(const float *__restrict__ cl,
+                                               const float *__restrict__ fgrid, const PersonCoords &pc,
+                                               const float *__restrict__ props,
+                                               const int32_t *__restrict__ frame_of, const fvp_person_spec &s,
+                                               float *__restrict__ cubes, float *__restrict__ planes,
+                                               float *__restrict__ offset, int P, int V, int J, int Jst,
+                                               int H, int W, int xmap, int xsplit, int zsplit,
+                                               unsigned pix_bytes, int xy_direct) {
+    constexpr int JP = JPL * LPV;  // joint slots of the block
     __shared__ float lcam[OTF ? 64 * FVP_CAM_STRIDE : 1];  // OTF: camera records (V <= 64)
     // xy_direct: [wave][x][joint slot] per-wave z maxima, stored at the block's end
     constexpr bool DXY = LPV <= 4;
-    __shared__ unsigned lxy[DXY ? LPV * 64 * 4 * LPV : 1];
+    __shared__ unsigned lxy[DXY ? LPV * 64 * JP : 1];
     const int SX = s.bins[0], SY = s.bins[1], SZ = s.bins[2];
     // XCD-aware: each XCD runs whole proposals, so the rows of one proposal
     // (walking x together) share that XCD's L2 footprint (L2 hit 35 % with
@@ -279,8 +293,11 @@ __global__ __launch_bounds__(64 * LPV) void person_cl_kernel(const float *__rest
     const Window w = person_window(props + (size_t)p * 7, s);
     if (offset && y == 0 && part == 0 && threadIdx.x < 3) {
         const int a = threadIdx.x;
+        // (JPL == 8: the window's element by selects -- indexing the register-held struct
+        // by thread puts it in scratch; the fp32 kernels keep their code as it was)
+        const int ca = JPL == 8 ? (a == 0 ? w.ctl[0] : a == 1 ? w.ctl[1] : w.ctl[2]) : w.ctl[a];
         offset[(size_t)p * 3 + a] =
-            ((float)w.ctl[a] / (float)(s.fine[a] - 1)) * s.whole_size[a] - s.whole_size[a] / 2.0f + s.ind_size[a] / 2.0f;
+            ((float)ca / (float)(s.fine[a] - 1)) * s.whole_size[a] - s.whole_size[a] / 2.0f + s.ind_size[a] / 2.0f;
     }
     const int lane = threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
     const int zl = zc * 64 + (int)threadIdx.x / LPV, q = threadIdx.x % LPV;
@@ -320,7 +337,9 @@ __global__ __launch_bounds__(64 * LPV) void person_cl_kernel(const float *__rest
     // mean is clamped and +0.0f turns a -0 into +0), so unsigned order is float
     // order with NaN on top (torch.max: NaN wins) -- one v_max_u32 per step
     // instead of a NaN-aware float max (compares + select); +0 is neutral
-    unsigned yzacc[4] = {0u, 0u, 0u, 0u};
+    unsigned yzacc[JPL];
+#pragma unroll
+    for (int k = 0; k < JPL; ++k) yzacc[k] = 0u;
 
     // xy_direct (host: one x part, one z chunk, S <= 64, LPV <= 4 for every joint
     // slice): the block owns its row's xy cells, so the per-wave z maxima go to LDS
@@ -329,7 +348,7 @@ __global__ __launch_bounds__(64 * LPV) void person_cl_kernel(const float *__rest
     // vmcnt and the next taps wait on them)
     const bool defer = DXY && planes && xy_direct;
     if (defer) {
-        for (int e = lane; e < 64 * 4 * LPV; e += 64) lxy[wave * 64 * 4 * LPV + e] = 0u;
+        for (int e = lane; e < 64 * JP; e += 64) lxy[wave * 64 * JP + e] = 0u;
     }
     int x_lo = xpart * SX / xsplit, x_hi = (xpart + 1) * SX / xsplit;
     if (!cubes) {
@@ -347,13 +366,13 @@ __global__ __launch_bounds__(64 * LPV) void person_cl_kernel(const float *__rest
         const int gx = w.ctl[0] + x;
         const bool xin = !w.skip && gx >= w.start[0] && gx < w.end[0];
         const bool valid = xin && zin && row_in;
-        float acc[4];
-        person_voxel_sum<LPV, OTF, CASC, MODE>(acc, valid, gx, gy, gz, grs, lcam, rt, pc, s, frame_cl, img, qo, q, V, GV,
+        float acc[JPL];
+        person_voxel_sum<LPV, OTF, CASC, MODE, JPL>(acc, valid, gx, gy, gz, grs, lcam, rt, pc, s, frame_cl, img, qo, q, V, GV,
                                                W, H, sxs, sys, pix_bytes);
-        float o[4];
-        unsigned ou[4];
+        float o[JPL];
+        unsigned ou[JPL];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
+        for (int k = 0; k < JPL; ++k) {
             // clamp(0,1) of the mean; +0.0f turns a -0 into +0 (unsigned max order below)
             o[k] = valid ? clampf(acc[k] / fV, 0.0f, 1.0f) + 0.0f : 0.0f;
             ou[k] = zok ? __builtin_bit_cast(unsigned, o[k]) : 0u;  // beyond the cube: neutral
@@ -364,43 +383,50 @@ __global__ __launch_bounds__(64 * LPV) void person_cl_kernel(const float *__rest
         }
         if (cubes && zok) {
 #pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (4 * q + k < J) cubes[((size_t)p * Jst + 4 * q + k) * S3 + ((size_t)x * SY + y) * SZ + zl] = o[k];
+            for (int k = 0; k < JPL; ++k)
+                if (JPL * q + k < J) cubes[((size_t)p * Jst + JPL * q + k) * S3 + ((size_t)x * SY + y) * SZ + zl] = o[k];
         }
         if (planes) {
 #pragma unroll
-            for (int k = 0; k < 4; ++k) yzacc[k] = max(yzacc[k], ou[k]);
+            for (int k = 0; k < JPL; ++k) yzacc[k] = max(yzacc[k], ou[k]);
             // this wave's z-range maxima (all lanes: their slot's), four independent
-            // VALU chains; lane L < 4 LPV then holds joint 4 (L % LPV) + L / LPV
-            unsigned zm[4];
+            // VALU chains; lane L < JPL LPV then holds joint JPL (L % LPV) + L / LPV
+            unsigned zm[JPL];
 #pragma unroll
-            for (int k = 0; k < 4; ++k) zm[k] = slot_umax<LPV>(ou[k]);
+            for (int k = 0; k < JPL; ++k) zm[k] = slot_umax<LPV>(ou[k]);
             const int kk = lane / LPV;  // q == lane % LPV
-            const unsigned mv = kk == 0 ? zm[0] : kk == 1 ? zm[1] : kk == 2 ? zm[2] : zm[3];
+            unsigned mv;
+            if constexpr (JPL == 4) {
+                mv = kk == 0 ? zm[0] : kk == 1 ? zm[1] : kk == 2 ? zm[2] : zm[3];
+            } else {
+                mv = zm[JPL - 1];
+#pragma unroll
+                for (int k = JPL - 2; k >= 0; --k) mv = kk == k ? zm[k] : mv;
+            }
             if (defer) {
-                if (lane < 4 * LPV) lxy[(wave * 64 + x) * (4 * LPV) + 4 * q + kk] = mv;
-            } else if (MODE != 6 && lane < 4 * LPV && 4 * q + kk < J && mv != 0u) {
+                if (lane < JP) lxy[(wave * 64 + x) * JP + JPL * q + kk] = mv;
+            } else if (MODE != 6 && lane < JP && JPL * q + kk < J && mv != 0u) {
                 // into the pre-zeroed plane (+0 cannot raise it)
-                atomicMax(reinterpret_cast<unsigned *>(xy_pl) + ((size_t)(4 * q + kk) * SX + x) * SY + y, mv);
+                atomicMax(reinterpret_cast<unsigned *>(xy_pl) + ((size_t)(JPL * q + kk) * SX + x) * SY + y, mv);
             }
             if (zok) {
 #pragma unroll
-                for (int k = 0; k < 4; ++k) {
+                for (int k = 0; k < JPL; ++k) {
                     // +0 cannot raise the pre-zeroed plane: skip those atomics (most of the 64^3 cube)
                     const unsigned u = ou[k];
-                    if (MODE == 8 && 4 * q + k < J && u != 0u)  // probe: plain stores instead (wrong maxima)
-                        reinterpret_cast<unsigned *>(xz_pl)[((size_t)(4 * q + k) * SX + x) * SZ + zl] = u;
-                    else if (MODE != 5 && MODE != 8 && (MODE != 7 || (zl & 1) == 0) && 4 * q + k < J && u != 0u)
-                        atomicMax(reinterpret_cast<unsigned *>(xz_pl) + ((size_t)(4 * q + k) * SX + x) * SZ + zl, u);
+                    if (MODE == 8 && JPL * q + k < J && u != 0u)  // probe: plain stores instead (wrong maxima)
+                        reinterpret_cast<unsigned *>(xz_pl)[((size_t)(JPL * q + k) * SX + x) * SZ + zl] = u;
+                    else if (MODE != 5 && MODE != 8 && (MODE != 7 || (zl & 1) == 0) && JPL * q + k < J && u != 0u)
+                        atomicMax(reinterpret_cast<unsigned *>(xz_pl) + ((size_t)(JPL * q + k) * SX + x) * SZ + zl, u);
                 }
             }
         }
     }
     if (planes && zok) {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (4 * q + k >= J) continue;
-            float *dst = yz_pl + ((size_t)(4 * q + k) * SY + y) * SZ + zl;
+        for (int k = 0; k < JPL; ++k) {
+            if (JPL * q + k >= J) continue;
+            float *dst = yz_pl + ((size_t)(JPL * q + k) * SY + y) * SZ + zl;
             const unsigned u = yzacc[k];
             if (xsplit == 1) *dst = __builtin_bit_cast(float, u);
             else if (u != 0u) atomicMax(reinterpret_cast<unsigned *>(dst), u);  // pre-zeroed plane
@@ -416,10 +442,39 @@ __global__ __launch_bounds__(64 * LPV) void person_cl_kernel(const float *__rest
             const int xi = x_lo + e / J, j = e - (e / J) * J;
             unsigned m = 0u;
 #pragma unroll
-            for (int wv = 0; wv < LPV; ++wv) m = max(m, lxy[(wv * 64 + xi) * (4 * LPV) + j]);
+            for (int wv = 0; wv < LPV; ++wv) m = max(m, lxy[(wv * 64 + xi) * JP + j]);
             if (MODE != 6 && m != 0u) xy_pl[((size_t)j * SX + xi) * SY + y] = __builtin_bit_cast(float, m);
         }
     }
+}
+
+template <int LPV, bool OTF, bool CASC, int MODE = 0>
+__global__ __launch_bounds__(64 * LPV) void person_cl_kernel(const float *__restrict__ cl,
+                                                             const float *__restrict__ fgrid, PersonCoords pc,
+                                                             const float *__restrict__ props,
+                                                             const int32_t *__restrict__ frame_of, fvp_person_spec s,
+                                                             float *__restrict__ cubes, float *__restrict__ planes,
+                                                             float *__restrict__ offset, int P, int V, int J, int Jst,
+                                                             int H, int W, int xmap, int xsplit, int zsplit,
+                                                             unsigned pix_bytes, int xy_direct) {
+    person_cl_body<LPV, OTF, CASC, MODE, 4>(cl, fgrid, pc, props, frame_of, s, cubes, planes, offset, P, V, J, Jst, H, W,
+                                            xmap, xsplit, zsplit, pix_bytes, xy_direct);
+}
+
+// The same on fp16 channels-last pixels read in place (cached fine grid): 8 joints
+// per lane, blocks of 64 z x LPV threads with LPV = 1 / 2 / 4 for J <= 8 / 16 / 32.
+template <int LPV, bool CASC>
+__global__ __launch_bounds__(64 * LPV) void person_cl_h8_kernel(const float *__restrict__ cl,
+                                                                const float *__restrict__ fgrid, PersonCoords pc,
+                                                                const float *__restrict__ props,
+                                                                const int32_t *__restrict__ frame_of,
+                                                                fvp_person_spec s, float *__restrict__ cubes,
+                                                                float *__restrict__ planes, float *__restrict__ offset,
+                                                                int P, int V, int J, int Jst, int H, int W, int xmap,
+                                                                int xsplit, int zsplit, unsigned pix_bytes,
+                                                                int xy_direct) {
+    person_cl_body<LPV, false, CASC, 0, 8>(cl, fgrid, pc, props, frame_of, s, cubes, planes, offset, P, V, J, Jst, H, W,
+                                           xmap, xsplit, zsplit, pix_bytes, xy_direct);
 }
 
 // Small launches (per-frame calls) split each row's x walk over 2-4 blocks.
@@ -428,7 +483,7 @@ static int person_xsplit(int P, int SY) {
     return rows >= 4096 ? 1 : rows >= 1024 ? 2 : 4;
 }
 
-template <int LPV, bool OTF, bool CASC>
+template <int LPV, bool OTF, bool CASC, int JPL = 4>
 static void launch_person_cl(const float *cl, const float *fgrid, const PersonCoords &pc, const float *props,
                              const int32_t *frame_of, const fvp_person_spec &s, float *cubes, float *planes,
                              float *offset, int P, int V, int J, int Jst, int H, int W, unsigned pix_bytes,
@@ -445,9 +500,14 @@ static void launch_person_cl(const float *cl, const float *fgrid, const PersonCo
     // each (the xy and xz maxima combine across blocks through atomics; yz is per
     // (y, z)).
     const int xmap = 1, xsplit = person_xsplit(P, SY), zsplit = (s.bins[2] + 63) / 64;
-    hipLaunchKernelGGL((person_cl_kernel<LPV, OTF, CASC>), dim3((unsigned)((long long)P * SY * xsplit * zsplit)),
-                       dim3(64 * LPV), 0, st, cl, fgrid, pc, props, frame_of, s, cubes, planes, offset, P, V, J, Jst, H,
-                       W, xmap, xsplit, zsplit, pix_bytes, xy_direct);
+    const dim3 grid((unsigned)((long long)P * SY * xsplit * zsplit));
+    if constexpr (JPL == 8)
+        hipLaunchKernelGGL((person_cl_h8_kernel<LPV, CASC>), grid, dim3(64 * LPV), 0, st, cl, fgrid, pc, props, frame_of,
+                           s, cubes, planes, offset, P, V, J, Jst, H, W, xmap, xsplit, zsplit, pix_bytes, xy_direct);
+    else
+        hipLaunchKernelGGL((person_cl_kernel<LPV, OTF, CASC>), grid, dim3(64 * LPV), 0, st, cl, fgrid, pc, props,
+                           frame_of, s, cubes, planes, offset, P, V, J, Jst, H, W, xmap, xsplit, zsplit, pix_bytes,
+                           xy_direct);
 }
 
 }  // namespace fvp
@@ -482,7 +542,8 @@ constexpr int kPersonSlice = 32;
 static int person_planes_any(const float *heatmaps, int cp, int B, int V, int J, int H, int W,
                              const float *fine_grid, const PersonCoords *pc, const fvp_person_spec *spec,
                              const float *proposals, const int32_t *frame_of, int P, float *cubes, float *planes,
-                             float *offset, void *workspace, size_t workspace_bytes, void *stream) {
+                             float *offset, void *workspace, size_t workspace_bytes, void *stream,
+                             bool cl_half = false) {
     if (!heatmaps || !spec || (!fine_grid && !pc)) return FVP_ERR_NULL;
     if (P <= 0) return FVP_OK;
     if (!proposals) return FVP_ERR_NULL;
@@ -497,7 +558,11 @@ static int person_planes_any(const float *heatmaps, int cp, int B, int V, int J,
     if (!pc && (long long)spec->fine[0] * spec->fine[1] * spec->fine[2] * FVP_GRID_SLOTS(V) * 8 > 0xfffff000LL)
         return FVP_ERR_SHAPE;
     const int J1 = J < kPersonSlice ? J : kPersonSlice;
-    if (cp) {
+    if (cl_half) {  // fp16 pixels, cp in fp16 elements (as fvp_voxelize_cl_f16); cached fine grid only
+        if (pc || cp <= 0 || cp % 8 || cp < J || ((unsigned long long)heatmaps & 15ull) != 0 ||
+            (unsigned long long)H * W * cp * 2 > 0x7fffffffull)
+            return FVP_ERR_SHAPE;
+    } else if (cp) {
         const int jl = ((J - 1) / kPersonSlice) * kPersonSlice;
         if (cp % 4 || cp < jl + 4 * lanes_per_voxel(J - jl) || (size_t)H * W * cp * 4 > 0x7fffffffull)
             return FVP_ERR_SHAPE;
@@ -510,7 +575,7 @@ static int person_planes_any(const float *heatmaps, int cp, int B, int V, int J,
     // xy_direct): one x part, one z chunk, S <= 64 and every joint slice at <= 4
     // lanes per voxel
     const int xsplit = person_xsplit(P, SY);
-    const int xy_direct = (planes && xsplit == 1 && SZ <= 64 && SX <= 64 && J <= 16) ? 1 : 0;
+    const int xy_direct = (planes && xsplit == 1 && SZ <= 64 && SX <= 64 && (J <= 16 || cl_half)) ? 1 : 0;
     if (planes) {  // xy, xz (and yz when x is split) hold maxima over non-negative floats: from +0
         const size_t n = (xsplit > 1 ? 3 : 2) * (size_t)P * J * SX * SY;
         const hipError_t e = hipMemsetAsync(planes, 0, n * 4, st);
@@ -521,6 +586,27 @@ static int person_planes_any(const float *heatmaps, int cp, int B, int V, int J,
     const size_t HW = (size_t)H * W, S2 = (size_t)SX * SY, S3 = S2 * SZ;
     for (int j0 = 0; j0 < J; j0 += kPersonSlice) {
         const int Jc = J - j0 < kPersonSlice ? J - j0 : kPersonSlice;
+        if (cl_half) {
+            const float *clh = reinterpret_cast<const float *>(reinterpret_cast<const _Float16 *>(heatmaps) + j0);
+            const unsigned pixb = 2u * (unsigned)cp;
+            float *cb = cubes ? cubes + j0 * S3 : nullptr;
+            float *pl = planes ? planes + j0 * S2 : nullptr;
+            auto go = [&](auto lpv) {
+                constexpr int L = decltype(lpv)::value;
+                if (V > 16)
+                    launch_person_cl<L, false, true, 8>(clh, fine_grid, c, proposals, frame_of, *spec, cb, pl, offset, P,
+                                                        V, Jc, J, H, W, pixb, xy_direct, st);
+                else
+                    launch_person_cl<L, false, false, 8>(clh, fine_grid, c, proposals, frame_of, *spec, cb, pl, offset,
+                                                         P, V, Jc, J, H, W, pixb, xy_direct, st);
+            };
+            switch (lanes_per_voxel_h(Jc)) {
+                case 1: go(std::integral_constant<int, 1>{}); break;
+                case 2: go(std::integral_constant<int, 2>{}); break;
+                default: go(std::integral_constant<int, 4>{}); break;
+            }
+            continue;
+        }
         const float *cl = cp ? heatmaps + j0 : reinterpret_cast<const float *>(workspace);
         const unsigned pix_bytes = 4u * (unsigned)(cp ? cp : 4 * lanes_per_voxel(Jc));
         float *cb = cubes ? cubes + j0 * S3 : nullptr;
@@ -584,4 +670,15 @@ extern "C" int fvp_person_planes_cl(const float *heatmaps_cl, int cp, int B, int
     if (cp <= 0) return FVP_ERR_SHAPE;
     return fvp::person_planes_any(heatmaps_cl, cp, B, V, J, H, W, fine_grid, nullptr, spec, proposals, frame_of, P,
                                   cubes, planes, offset, nullptr, 0, stream);
+}
+
+extern "C" int fvp_person_planes_cl_f16(const void *heatmaps_cl, int cp, int B, int V, int J, int H, int W,
+                                        const float *fine_grid, const fvp_person_spec *spec, const float *proposals,
+                                        const int32_t *frame_of, int P, float *cubes, float *planes, float *offset,
+                                        void *stream) {
+    if (!heatmaps_cl || !fine_grid || !spec) return FVP_ERR_NULL;
+    if (cp <= 0 || cp % 8 || cp < J || J > FVP_MAX_JOINTS || ((unsigned long long)heatmaps_cl & 15ull) != 0)
+        return FVP_ERR_SHAPE;
+    return fvp::person_planes_any(reinterpret_cast<const float *>(heatmaps_cl), cp, B, V, J, H, W, fine_grid, nullptr,
+                                  spec, proposals, frame_of, P, cubes, planes, offset, nullptr, 0, stream, true);
 }

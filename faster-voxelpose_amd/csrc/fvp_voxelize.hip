@@ -16,6 +16,9 @@
 //   fp16: heatmaps_to_pairs [B][V][J][H][W] -> [b][V][H][W+1] 64-B entries
 //         holding pixels x0 and x0+1 of a row (J <= 16): 2 loads per
 //         voxel-camera, half the bytes through L1 (fp16 -> fp32 is exact).
+// fp16 heatmaps already channels-last ([B][V][H][W][cp] fp16, fvp_voxelize_cl_f16)
+// are read in place: a lane's 16 B = 8 joints, so a voxel takes 1 / 2 / 4 lanes
+// for J <= 8 / 16 / 32 and a voxel-camera's 4 loads come from half the lanes.
 // Out-of-image taps use an out-of-range offset and read 0 through the buffer
 // descriptor's range check (= grid_sample's zero padding).  The chunk's copy
 // stays in the 256 MB Infinity Cache between the two launches.
@@ -106,7 +109,10 @@ __device__ __forceinline__ void store_stage(const float *__restrict__ stage, int
     }
 }
 
-template <int LPV, bool PAIR, bool OTF, bool CASC, int NF>
+// JPL joints per lane: 4 (a lane's 16 B = 4 fp32 joints, or the pair table's 2 x 4
+// fp16) or 8 (fp16 channels-last pixels read in place: 16 B = 8 fp16 joints, so a
+// voxel needs half the lanes and a wave's four tap loads serve twice the voxels).
+template <int LPV, bool PAIR, bool OTF, bool CASC, int NF, int JPL = 4>
 __device__ __forceinline__ void voxelize_body(const void *__restrict__ tab, const CoordSource &src_,
                                                        const int32_t *__restrict__ grid_index, int frame0,
                                                        float *__restrict__ cube, float *__restrict__ xy, int V, int J,
@@ -114,7 +120,12 @@ __device__ __forceinline__ void voxelize_body(const void *__restrict__ tab, cons
                                                        int col_blocks, int SP, int band, unsigned pixb,
                                                        bool cube16) {
     static_assert(!PAIR || LPV == 4, "the fp16 pair table has 4 lanes per voxel");
-    constexpr int JP = 4 * LPV;
+    static_assert(JPL == 4 || (JPL == 8 && !PAIR && NF == 1), "fp16 channels-last: one frame per pixel, no table");
+    constexpr int JP = JPL * LPV;
+    // 8 joints per lane with the 16-camera cascade under the cached-grid kernel's
+    // 64 VGPRs: the completed blocks' sums wait in the voxel's own stage slots (LDS,
+    // written again only by this lane, at the end) instead of 8 more registers
+    constexpr bool PARK = JPL == 8 && CASC && !OTF;
     constexpr int VPP = 256 / LPV;  // voxels per pass
     constexpr int CPG = 2 * LPV;    // cameras per grid load (2 per lane)
     extern __shared__ __attribute__((aligned(16))) float stage[];  // [NF][JP][SP] (+ OTF camera records)
@@ -173,11 +184,11 @@ __device__ __forceinline__ void voxelize_body(const void *__restrict__ tab, cons
         const int zl = sl / ncols, cl = sl - zl * ncols;
         const int ii = cl * Z + zl;
         const long long gn = (long long)(c0 + cl) * Z + zl;
-        float acc[NF][4], blk[NF][4];  // blk (CASC): completed 16-camera blocks (view_sum order)
+        float acc[NF][JPL], blk[NF][JPL];  // blk (CASC): completed 16-camera blocks (view_sum order)
 #pragma unroll
         for (int f = 0; f < NF; ++f)
 #pragma unroll
-            for (int m = 0; m < 4; ++m) acc[f][m] = blk[f][m] = 0.0f;
+            for (int m = 0; m < JPL; ++m) acc[f][m] = blk[f][m] = 0.0f;
         float wx_ = 0.f, wy_ = 0.f, wz_ = 0.f;  // OTF: voxel centre (compute_grid, project_whole.py:43-79)
         if constexpr (OTF) {
             const int iz = zl;
@@ -188,6 +199,26 @@ __device__ __forceinline__ void voxelize_body(const void *__restrict__ tab, cons
             wz_ = axis_coord(src_.gs.start[2], src_.gs.end[2], Z, iz, src_.gs.center[2]);
         }
         for (int v0 = 0; v0 < V; v0 += CPG) {
+            if constexpr (PARK) {
+                // a block of 16 cameras is complete (CPG divides 16, so only ever at a
+                // group's first camera): fold it into the parked sum, before this
+                // group's taps are set up (fewest live registers)
+                if ((v0 & 15) == 0 && v0 > 0) {
+                    if (valid) {
+                        // (the slot addresses are formed here, behind an opaque copy, or the
+                        // compiler keeps all 8 of them in registers across the camera loop)
+                        int slot = JPL * q * SP + ii;
+                        asm volatile("" : "+v"(slot));
+#pragma unroll
+                        for (int m = 0; m < JPL; ++m) {
+                            float *p = stage + slot + m * SP;
+                            *p = (v0 == 16 ? 0.0f : *p) + acc[0][m];
+                        }
+                    }
+#pragma unroll
+                    for (int m = 0; m < JPL; ++m) acc[0][m] = 0.0f;
+                }
+            }
             // cameras v0+2q, v0+2q+1 of voxel n0+ii (past V: padding, unused)
             float g[4];
             if constexpr (OTF) {
@@ -214,12 +245,12 @@ __device__ __forceinline__ void voxelize_body(const void *__restrict__ tab, cons
                 constexpr int S = k >> 1;  // lane of the group that set this camera up
                 const int v = v0 + k;
                 if (v >= V) return;
-                if constexpr (CASC) {
+                if constexpr (CASC && !PARK) {
                     if ((v & 15) == 0 && v > 0) {  // a block of 16 cameras is complete: fold it (fvp_device.h)
 #pragma unroll
                         for (int f = 0; f < NF; ++f)
 #pragma unroll
-                            for (int m = 0; m < 4; ++m) {
+                            for (int m = 0; m < JPL; ++m) {
                                 blk[f][m] = blk[f][m] + acc[f][m];
                                 acc[f][m] = 0.0f;
                             }
@@ -266,6 +297,16 @@ __device__ __forceinline__ void voxelize_body(const void *__restrict__ tab, cons
                         c[f] = __builtin_amdgcn_raw_buffer_load_b128(rs, o[2] + f * pix + qo, 0, 0);
                         d[f] = __builtin_amdgcn_raw_buffer_load_b128(rs, o[3] + f * pix + qo, 0, 0);
                     }
+                    if constexpr (JPL == 8) {
+                        // word i of a pixel piece = joints 8q+2i (low half), 8q+2i+1 (high half):
+                        // fd*w3 + (fc*w2 + (fb*w1 + fa*w0)), the fp16 taps converted inside the fmas
+                        static_for(std::make_integer_sequence<int, 8>{}, [&](auto mc) {
+                            constexpr int m = decltype(mc)::value, HI = m & 1, wd = m >> 1;
+                            const float t = fma_h<HI>(a[0][wd], w[0], -0.0f);
+                            acc[0][m] = acc[0][m] + fma_h<HI>(d[0][wd], w[3],
+                                                              fma_h<HI>(c[0][wd], w[2], fma_h<HI>(bq[0][wd], w[1], t)));
+                        });
+                    } else {
 #pragma unroll
                     for (int f = 0; f < NF; ++f)
 #pragma unroll
@@ -277,6 +318,7 @@ __device__ __forceinline__ void voxelize_body(const void *__restrict__ tab, cons
                             acc[f][m] = acc[f][m] + __builtin_fmaf(fd, w[3], __builtin_fmaf(fc, w[2],
                                                                    __builtin_fmaf(fb, w[1], fa * w[0])));
                         }
+                    }
                 }
             });
         }
@@ -284,13 +326,25 @@ __device__ __forceinline__ void voxelize_body(const void *__restrict__ tab, cons
 #pragma unroll
         for (int f = 0; f < NF; ++f)
 #pragma unroll
-            for (int m = 0; m < 4; ++m) acc[f][m] = acc[f][m] + (CASC ? blk[f][m] : 0.0f);
-        if (valid) {
+            for (int m = 0; m < JPL; ++m) {
+                if constexpr (!PARK) acc[f][m] = acc[f][m] + (CASC ? blk[f][m] : 0.0f);
+            }
+        if constexpr (PARK) {
+            int slot = JPL * q * SP + ii;
+            asm volatile("" : "+v"(slot));
+            if (valid) {
+#pragma unroll
+                for (int m = 0; m < JPL; ++m) {
+                    float *p = stage + slot + m * SP;
+                    *p = clampf((acc[0][m] + *p) / fV, 0.0f, 1.0f);
+                }
+            }
+        } else if (valid) {
 #pragma unroll
             for (int f = 0; f < NF; ++f)
 #pragma unroll
-                for (int m = 0; m < 4; ++m)
-                    stage[(f * JP + 4 * q + m) * SP + ii] = clampf(acc[f][m] / fV, 0.0f, 1.0f);
+                for (int m = 0; m < JPL; ++m)
+                    stage[(f * JP + JPL * q + m) * SP + ii] = clampf(acc[f][m] / fV, 0.0f, 1.0f);
         }
     }
     __syncthreads();
@@ -324,6 +378,30 @@ __global__ __launch_bounds__(256) void voxelize_cams_kernel(const void *__restri
     static_assert(OTF, "on-the-fly kernel");
     voxelize_body<LPV, PAIR, OTF, CASC, NF>(tab, src, grid_index, frame0, cube, xy, V, J, Jst, H, W, X, Y, Z, cols,
                                             col_blocks, SP, band, pixb, cube16);
+}
+
+// The same gathers on fp16 channels-last pixels read in place (8 joints per
+// lane): cached grid within 64 VGPRs, on the fly unconstrained, as above.
+template <int LPV, bool CASC>
+__global__ __launch_bounds__(256, 8) void voxelize_h8_kernel(const void *__restrict__ tab, CoordSource src,
+                                                             const int32_t *__restrict__ grid_index, int frame0,
+                                                             float *__restrict__ cube, float *__restrict__ xy, int V,
+                                                             int J, int Jst, int H, int W, int X, int Y, int Z,
+                                                             int cols, int col_blocks, int SP, int band,
+                                                             unsigned pixb, bool cube16) {
+    voxelize_body<LPV, false, false, CASC, 1, 8>(tab, src, grid_index, frame0, cube, xy, V, J, Jst, H, W, X, Y, Z, cols,
+                                                 col_blocks, SP, band, pixb, cube16);
+}
+
+template <int LPV, bool CASC>
+__global__ __launch_bounds__(256) void voxelize_cams_h8_kernel(const void *__restrict__ tab, CoordSource src,
+                                                               const int32_t *__restrict__ grid_index, int frame0,
+                                                               float *__restrict__ cube, float *__restrict__ xy, int V,
+                                                               int J, int Jst, int H, int W, int X, int Y, int Z,
+                                                               int cols, int col_blocks, int SP, int band,
+                                                               unsigned pixb, bool cube16) {
+    voxelize_body<LPV, false, true, CASC, 1, 8>(tab, src, grid_index, frame0, cube, xy, V, J, Jst, H, W, X, Y, Z, cols,
+                                                col_blocks, SP, band, pixb, cube16);
 }
 
 // [V][N][2] -> [N][GV][2], padding slots (-2,-2) (off-image)
@@ -399,7 +477,7 @@ struct GatherCfg {
     size_t lds;
 };
 
-template <int LPV, bool OTF>
+template <int LPV, bool OTF, int JPL = 4>  // (JPL = 8: the stage holds 8 * LPV joints, a pass 256 / LPV voxels)
 static int gather_cfg(int frames, int NF, int V, int X, int Y, int Z, GatherCfg &c) {
     // Column groups that tile the x-rows exactly (largest divisor of Y, if it
     // keeps at least half the columns), so the blocks can be walked in bands of
@@ -435,19 +513,25 @@ static int gather_cfg(int frames, int NF, int V, int X, int Y, int Z, GatherCfg 
     c.cols = cols;
     c.band = (big && Y % cols == 0 && X > kBandRows) ? kBandRows : 0;
     c.col_blocks = (X * Y + cols - 1) / cols;
-    c.SP = stage_pitch(LPV, cols, Z);
-    c.lds = (size_t)NF * 4 * LPV * c.SP * sizeof(float);
+    c.SP = stage_pitch(LPV * JPL / 4, cols, Z);
+    c.lds = (size_t)NF * JPL * LPV * c.SP * sizeof(float);
     if (OTF) c.lds = ((c.lds / 4 + 3) & ~(size_t)3) * 4 + (size_t)FVP_GRID_SLOTS(V) * FVP_CAM_STRIDE * sizeof(float);
     return c.lds > 160 * 1024 ? FVP_ERR_SHAPE : FVP_OK;
 }
 
-template <int LPV, bool PAIR, bool OTF, bool CASC, int NF>
+template <int LPV, bool PAIR, bool OTF, bool CASC, int NF, int JPL = 4>
 static void launch_gather(const void *tab, int f0, int nb, const GatherCfg &c, const CoordSource &src,
                           const int32_t *grid_index, int V, int J, int Jst, int H, int W, int X, int Y, int Z,
                           float *cube, float *xy, unsigned pixb, hipStream_t s) {
     const dim3 grid((unsigned)(nb / NF * c.col_blocks));
     const bool cube16 = ((unsigned long long)cube & 15ull) == 0;  // float4 epilogue stores
-    if constexpr (OTF)
+    if constexpr (JPL == 8 && OTF)
+        hipLaunchKernelGGL((voxelize_cams_h8_kernel<LPV, CASC>), grid, dim3(256), c.lds, s, tab, src, grid_index, f0,
+                           cube, xy, V, J, Jst, H, W, X, Y, Z, c.cols, c.col_blocks, c.SP, c.band, pixb, cube16);
+    else if constexpr (JPL == 8)
+        hipLaunchKernelGGL((voxelize_h8_kernel<LPV, CASC>), grid, dim3(256), c.lds, s, tab, src, grid_index, f0, cube,
+                           xy, V, J, Jst, H, W, X, Y, Z, c.cols, c.col_blocks, c.SP, c.band, pixb, cube16);
+    else if constexpr (OTF)
         hipLaunchKernelGGL((voxelize_cams_kernel<LPV, PAIR, true, CASC, NF>), grid, dim3(256), c.lds, s, tab, src,
                            grid_index, f0, cube, xy, V, J, Jst, H, W, X, Y, Z, c.cols, c.col_blocks, c.SP, c.band,
                            pixb, cube16);
@@ -514,6 +598,28 @@ static int run_direct(const float *hm_cl, int cp, int B, const VoxJob &j, const 
         case 2: return go(std::integral_constant<int, 2>{});
         case 4: return go(std::integral_constant<int, 4>{});
         default: return go(std::integral_constant<int, 8>{});
+    }
+}
+
+// The same for fp16 channels-last heatmaps ([B][V][H][W][cp] fp16): a pixel of
+// 16 joints is 32 B, a lane's 16-B load carries 8 joints, so a voxel takes 1 / 2 /
+// 4 lanes for J <= 8 / 16 / 32 and a wave's four tap loads cover twice the voxels.
+template <bool OTF, bool CASC>
+static int run_direct_h(const _Float16 *hm_cl, int cp, int B, const VoxJob &j, const CoordSource &src,
+                        hipStream_t s) {
+    const unsigned pixb = (unsigned)cp * 2u;
+    auto go = [&](auto lpv) -> int {
+        constexpr int LPV = decltype(lpv)::value;
+        GatherCfg c;
+        if (gather_cfg<LPV, OTF, 8>(B, 1, j.V, j.X, j.Y, j.Z, c) != FVP_OK) return FVP_ERR_SHAPE;
+        launch_gather<LPV, false, OTF, CASC, 1, 8>(hm_cl, 0, B, c, src, j.grid_index, j.V, j.J, j.Jst, j.H, j.W, j.X,
+                                                  j.Y, j.Z, j.cube, j.xy, pixb, s);
+        return (int)hipGetLastError();
+    };
+    switch (lanes_per_voxel_h(j.J)) {
+        case 1: return go(std::integral_constant<int, 1>{});
+        case 2: return go(std::integral_constant<int, 2>{});
+        default: return go(std::integral_constant<int, 4>{});
     }
 }
 
@@ -598,6 +704,34 @@ static int voxelize_cl_any(const float *hm_cl, int cp, int B, int V, int J, int 
                          xy ? xy + j0 * XY : nullptr};
         const int st = V > 16 ? run_direct<OTF, true>(hm_cl + j0, cp, B, job, src, s)
                               : run_direct<OTF, false>(hm_cl + j0, cp, B, job, src, s);
+        if (st != FVP_OK) return st;
+    }
+    return FVP_OK;
+}
+
+// fp16 channels-last input (cp in fp16 elements): a lane of the last slice may
+// read the 16-B piece that holds channels beyond cp -- the next pixel's first
+// channels, or 0 past the camera image (descriptor range) -- which only feed
+// joints >= J that are never stored.
+static int check_cl_half(const void *hm_cl, int cp, int J, int H, int W) {
+    if (cp <= 0 || cp % 8 || cp < J || J > FVP_MAX_JOINTS) return FVP_ERR_SHAPE;
+    if (((unsigned long long)hm_cl & 15ull) != 0) return FVP_ERR_SHAPE;               // 16-B pixel pieces
+    if ((unsigned long long)H * W * cp * 2 > 0x7fffffffull) return FVP_ERR_SHAPE;  // 32-bit tap offsets per camera image
+    return FVP_OK;
+}
+
+template <bool OTF>
+static int voxelize_cl_half_any(const _Float16 *hm_cl, int cp, int B, int V, int J, int H, int W,
+                                const CoordSource &src, const int32_t *grid_index, int X, int Y, int Z, float *cube,
+                                float *xy, hipStream_t s) {
+    const int st0 = check_cl_half(hm_cl, cp, J, H, W);
+    if (st0 != FVP_OK) return st0;
+    const size_t N = (size_t)X * Y * Z, XY = (size_t)X * Y;
+    for (int j0 = 0; j0 < J; j0 += kJointSlice) {
+        const VoxJob job{V, min(kJointSlice, J - j0), J, H, W, X, Y, Z, grid_index, cube ? cube + j0 * N : nullptr,
+                         xy ? xy + j0 * XY : nullptr};
+        const int st = V > 16 ? run_direct_h<OTF, true>(hm_cl + j0, cp, B, job, src, s)
+                              : run_direct_h<OTF, false>(hm_cl + j0, cp, B, job, src, s);
         if (st != FVP_OK) return st;
     }
     return FVP_OK;
@@ -807,7 +941,8 @@ namespace fvp {
 static int voxelize_cams_rows(const void *heatmaps, bool half, const float *hm_cl, int cp, int B, int V, int J, int H,
                               int W, const float *cams, const int32_t *grid_index, const float *resize_t,
                               const fvp_grid_spec *grid, const fvp_image_spec *img, int x0, int x1, float *cube,
-                              float *xy, void *workspace, size_t workspace_bytes, hipStream_t s) {
+                              float *xy, void *workspace, size_t workspace_bytes, hipStream_t s,
+                              bool cl_half = false) {
     if (!cams || !resize_t || !grid || !img) return FVP_ERR_NULL;
     const int Y = grid->bins[1], Z = grid->bins[2];
     if (x0 < 0 || x1 > grid->bins[0] || x0 >= x1) return FVP_ERR_SHAPE;
@@ -822,6 +957,9 @@ static int voxelize_cams_rows(const void *heatmaps, bool half, const float *hm_c
     src.gs = *grid;
     src.im = fvp::image_consts(*img);
     src.x_off = x0;
+    if (hm_cl && cl_half)
+        return voxelize_cl_half_any<true>(reinterpret_cast<const _Float16 *>(hm_cl), cp, B, V, J, H, W, src,
+                                          grid_index, X, Y, Z, cube, xy, s);
     if (hm_cl) return voxelize_cl_any<true>(hm_cl, cp, B, V, J, H, W, src, grid_index, X, Y, Z, cube, xy, s);
     if (half)
         return voxelize_any<true, _Float16>(reinterpret_cast<const _Float16 *>(heatmaps), B, V, J, H, W, src,
@@ -878,4 +1016,60 @@ extern "C" int fvp_voxelize_cl_cams_slab(const float *heatmaps_cl, int cp, int B
     if (!heatmaps_cl) return FVP_ERR_NULL;
     return fvp::voxelize_cams_rows(nullptr, false, heatmaps_cl, cp, B, V, J, H, W, cams, grid_index, resize_t, grid,
                                    img, x_begin, x_end, cube, xy, nullptr, 0, (hipStream_t)stream);
+}
+
+extern "C" int fvp_voxelize_cl_f16(const void *heatmaps_cl, int cp, int B, int V, int J, int H, int W,
+                                   const float *packed_grids, const int32_t *grid_index, int X, int Y, int Z,
+                                   float *cube, float *xy, void *stream) {
+    const int st = fvp::check_args(heatmaps_cl, B, V, J, H, W, packed_grids, X, Y, Z);
+    if (st != FVP_OK) return st;
+    const int sc = fvp::check_cl_half(heatmaps_cl, cp, J, H, W);
+    if (sc != FVP_OK) return sc;
+    if (!cube && !xy) return FVP_OK;
+    fvp::CoordSource src{};
+    src.grids = packed_grids;
+    return fvp::voxelize_cl_half_any<false>(reinterpret_cast<const _Float16 *>(heatmaps_cl), cp, B, V, J, H, W, src,
+                                            grid_index, X, Y, Z, cube, xy, (hipStream_t)stream);
+}
+
+extern "C" int fvp_voxelize_cl_cams_f16(const void *heatmaps_cl, int cp, int B, int V, int J, int H, int W,
+                                        const float *cams, const int32_t *grid_index, const float *resize_t,
+                                        const fvp_grid_spec *grid, const fvp_image_spec *img, float *cube, float *xy,
+                                        void *stream) {
+    if (!heatmaps_cl || !grid) return FVP_ERR_NULL;
+    const int sc = fvp::check_cl_half(heatmaps_cl, cp, J, H, W);
+    if (sc != FVP_OK) return sc;
+    return fvp::voxelize_cams_rows(nullptr, false, reinterpret_cast<const float *>(heatmaps_cl), cp, B, V, J, H, W,
+                                   cams, grid_index, resize_t, grid, img, 0, grid->bins[0], cube, xy, nullptr, 0,
+                                   (hipStream_t)stream, true);
+}
+
+extern "C" int fvp_voxelize_cl_cams_slab_f16(const void *heatmaps_cl, int cp, int B, int V, int J, int H, int W,
+                                             const float *cams, const int32_t *grid_index, const float *resize_t,
+                                             const fvp_grid_spec *grid, const fvp_image_spec *img, int x_begin,
+                                             int x_end, float *cube, float *xy, void *stream) {
+    if (!heatmaps_cl) return FVP_ERR_NULL;
+    const int sc = fvp::check_cl_half(heatmaps_cl, cp, J, H, W);
+    if (sc != FVP_OK) return sc;
+    return fvp::voxelize_cams_rows(nullptr, false, reinterpret_cast<const float *>(heatmaps_cl), cp, B, V, J, H, W,
+                                   cams, grid_index, resize_t, grid, img, x_begin, x_end, cube, xy, nullptr, 0,
+                                   (hipStream_t)stream, true);
+}
+
+extern "C" int fvp_nchw_to_nhwc_f16(const void *in, int in_half, int N, int C, int H, int W, int Cp, void *out,
+                                    void *stream) {
+    if (!in || !out) return FVP_ERR_NULL;
+    if (N <= 0 || C <= 0 || Cp < C || Cp % 8 || H <= 0 || W <= 0 || ((unsigned long long)out & 15ull) != 0)
+        return FVP_ERR_SHAPE;
+    const int G = Cp / 8;
+    const long long px = (long long)N * H * W, threads = px * G;
+    if ((threads + 255) / 256 > 0x7fffffffLL) return FVP_ERR_SHAPE;
+    const dim3 g((unsigned)((threads + 255) / 256)), blk(256);
+    if (in_half)
+        hipLaunchKernelGGL((fvp::planar_to_cl_half_kernel<_Float16>), g, blk, 0, (hipStream_t)stream,
+                           reinterpret_cast<const _Float16 *>(in), reinterpret_cast<uint4 *>(out), C, H * W, G, px);
+    else
+        hipLaunchKernelGGL((fvp::planar_to_cl_half_kernel<float>), g, blk, 0, (hipStream_t)stream,
+                           reinterpret_cast<const float *>(in), reinterpret_cast<uint4 *>(out), C, H * W, G, px);
+    return (int)hipGetLastError();
 }

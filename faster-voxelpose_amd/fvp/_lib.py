@@ -58,6 +58,17 @@ SIGNATURES = {
     "fvp_voxelize_cl_cams_slab": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                   ctypes.POINTER(GridSpec), ctypes.POINTER(ImageSpec), c_int, c_int, c_void_p,
                                   c_void_p, c_void_p],
+    "fvp_voxelize_cl_f16": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
+                            c_int, c_void_p, c_void_p, c_void_p],
+    "fvp_voxelize_cl_cams_f16": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                 ctypes.POINTER(GridSpec), ctypes.POINTER(ImageSpec), c_void_p, c_void_p, c_void_p],
+    "fvp_voxelize_cl_cams_slab_f16": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                      c_void_p, ctypes.POINTER(GridSpec), ctypes.POINTER(ImageSpec), c_int, c_int,
+                                      c_void_p, c_void_p, c_void_p],
+    "fvp_person_planes_cl_f16": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                 ctypes.POINTER(PersonSpec), c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                 c_void_p],
+    "fvp_nchw_to_nhwc_f16": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
     "fvp_nms_topk": [c_void_p, c_int, c_int, c_int, ctypes.c_longlong, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "fvp_nms_topk_columns": [c_void_p, c_int, c_int, c_int, ctypes.c_longlong, c_int, c_void_p, c_void_p, c_void_p,
                              c_void_p, c_int, c_int, c_void_p, c_void_p],

@@ -16,13 +16,36 @@ from . import _lib
 
 
 class ChannelsLastHeatmaps:
-    """Heatmaps [B, V, J, H, W] stored as ``t`` = [B, V, H, W, Cp] fp32 (Cp >= J)."""
+    """Heatmaps [B, V, J, H, W] stored as ``t`` = [B, V, H, W, Cp] fp32 (Cp >= J),
+    or fp16 with Cp % 8 == 0 and a 16-B aligned base: a 16-joint pixel is then
+    32 B and the gathers read 8 joints per 16-B lane load (fvp_voxelize_cl_f16;
+    the results are those of the fp16-rounded values computed in fp32)."""
 
     def __init__(self, t: torch.Tensor, num_joints: int):
-        if t.dim() != 5 or t.dtype != torch.float32 or not t.is_contiguous() or t.shape[4] < num_joints:
-            raise _lib.FvpError(f"fvp: channels-last heatmaps must be contiguous fp32 [B,V,H,W,Cp>=J], got "
+        if t.dim() != 5 or t.dtype not in (torch.float32, torch.float16) or not t.is_contiguous() \
+                or t.shape[4] < num_joints:
+            raise _lib.FvpError(f"fvp: channels-last heatmaps must be contiguous fp32 / fp16 [B,V,H,W,Cp>=J], got "
                                 f"{tuple(t.shape)} {t.dtype}")
+        if t.dtype == torch.float16 and (t.shape[4] % 8 or t.data_ptr() % 16):
+            raise _lib.FvpError(f"fvp: fp16 channels-last heatmaps need Cp % 8 == 0 and a 16-B aligned base, got "
+                                f"{tuple(t.shape)} {t.dtype} at offset {t.data_ptr() % 16} mod 16")
         self.t, self.J = t, int(num_joints)
+
+    @property
+    def dtype(self) -> torch.dtype:
+        return self.t.dtype
+
+    def half(self) -> "ChannelsLastHeatmaps":
+        """The fp16 copy of an fp32 object (Cp kept when a multiple of 8, else rounded up
+        with zero channels); self if already fp16."""
+        if self.t.dtype == torch.float16:
+            return self
+        cp = self.cp
+        if cp % 8 == 0:
+            return ChannelsLastHeatmaps(self.t.half(), self.J)
+        t = torch.zeros(self.t.shape[:4] + (8 * ((cp + 7) // 8),), dtype=torch.float16, device=self.t.device)
+        t[..., :cp] = self.t
+        return ChannelsLastHeatmaps(t, self.J)
 
     @property
     def shape(self) -> tuple:
@@ -38,8 +61,11 @@ class ChannelsLastHeatmaps:
         return self.t.shape[4]
 
     def planar(self) -> torch.Tensor:
-        """[B, V, J, H, W] fp32 (the reference layout), carrying this object (attach)."""
+        """[B, V, J, H, W] in this object's dtype (the reference layout), carrying this
+        object (attach)."""
         B, V, J, H, W = self.shape
+        if self.t.dtype == torch.float16:  # (tensor-typed interfaces only: the gathers read self.t)
+            return attach(self.t[..., :J].permute(0, 1, 4, 2, 3).contiguous(), self)
         out = torch.empty((B, V, J, H, W), dtype=torch.float32, device=self.t.device)
         if out.numel():
             from .ops import _ptr, _stream
@@ -86,12 +112,30 @@ def release_shared(heatmaps) -> None:
         del heatmaps._fvp_cl
 
 
-def to_channels_last(planar: torch.Tensor) -> ChannelsLastHeatmaps:
+def to_channels_last(planar: torch.Tensor, dtype: torch.dtype | None = None) -> ChannelsLastHeatmaps:
     """[B, V, J, H, W] fp32 on a HIP device -> its channels-last copy
     [B, V, H, W, 16 * ceil(J / 16)] (J <= 32), one float4 layout launch
-    (fvp_nchw_to_nhwc: the voxelize layout pass over the whole batch)."""
+    (fvp_nchw_to_nhwc: the voxelize layout pass over the whole batch).
+
+    dtype=torch.float16: planar fp32 or fp16 -> the fp16 channels-last copy
+    (fvp_nchw_to_nhwc_f16: fp32 values rounded to nearest even as
+    ``Tensor.half()``, 16-B stores, any J) -- the opt-in to the fp16 gathers."""
     from .ops import _ptr, _stream
 
+    if dtype is not None:
+        if dtype != torch.float16:
+            raise _lib.FvpError(f"fvp: to_channels_last: dtype must be None or torch.float16, got {dtype}")
+        if planar.dim() != 5 or planar.dtype not in (torch.float32, torch.float16) or planar.device.type != "cuda":
+            raise _lib.FvpError(f"fvp: to_channels_last(dtype=float16) takes fp32 / fp16 [B,V,J,H,W] on a HIP "
+                                f"device, got {tuple(planar.shape)} {planar.dtype} {planar.device}")
+        B, V, J, H, W = planar.shape
+        cp = 16 * ((J + 15) // 16)
+        src = planar.contiguous()
+        t = torch.empty((B, V, H, W, cp), dtype=torch.float16, device=planar.device)
+        if t.numel():
+            _lib.call("fvp_nchw_to_nhwc_f16", _ptr(src), int(src.dtype == torch.float16), B * V, J, H, W, cp,
+                      _ptr(t), _stream(t))
+        return ChannelsLastHeatmaps(t, J)
     if planar.dim() != 5 or planar.dtype != torch.float32 or planar.device.type != "cuda":
         raise _lib.FvpError(f"fvp: to_channels_last takes fp32 [B,V,J,H,W] on a HIP device, got "
                             f"{tuple(planar.shape)} {planar.dtype} {planar.device}")

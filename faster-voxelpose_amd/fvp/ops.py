@@ -254,10 +254,16 @@ def _grid_index(grid_index: Optional[torch.Tensor], B: int, S: int, device) -> O
 def _cl_input(heatmaps_cl: torch.Tensor, J: int) -> torch.Tensor:
     if heatmaps_cl.device.type != "cuda":
         raise _lib.FvpError(f"fvp: heatmaps must be on a HIP device, got {heatmaps_cl.device}")
-    if heatmaps_cl.dim() != 5 or heatmaps_cl.dtype != torch.float32 or heatmaps_cl.shape[4] < J:
-        raise _lib.FvpError(f"fvp: channels-last heatmaps must be fp32 [B,V,H,W,Cp>=J], got "
+    if heatmaps_cl.dim() != 5 or heatmaps_cl.dtype not in (torch.float32, torch.float16) or heatmaps_cl.shape[4] < J:
+        raise _lib.FvpError(f"fvp: channels-last heatmaps must be fp32 / fp16 [B,V,H,W,Cp>=J], got "
                             f"{tuple(heatmaps_cl.shape)} {heatmaps_cl.dtype}")
     return heatmaps_cl.contiguous()
+
+
+def _f16(name: str, hm: torch.Tensor) -> str:
+    """The entry point for the channels-last heatmaps' dtype (fp16: its _f16 twin, which
+    checks cp % 8 and the base alignment on the host)."""
+    return name + "_f16" if hm.dtype == torch.float16 else name
 
 
 @_custom_op("fvp::voxelize_cl", mutates_args=(), device_types="cuda")
@@ -277,7 +283,7 @@ def voxelize_cl(heatmaps_cl: torch.Tensor, J: int, packed_grids: torch.Tensor, g
     xy = torch.empty((B, J, X, Y) if want_xy else (0,), dtype=torch.float32, device=hm.device)
     if B == 0:
         return cube, xy
-    _lib.call("fvp_voxelize_cl", _ptr(hm), cp, B, V, J, H, W, _ptr(pg), _ptr(gi), X, Y, Z,
+    _lib.call(_f16("fvp_voxelize_cl", hm), _ptr(hm), cp, B, V, J, H, W, _ptr(pg), _ptr(gi), X, Y, Z,
               _ptr(cube) if want_cube else None, _ptr(xy) if want_xy else None, _stream(hm))
     return cube, xy
 
@@ -285,8 +291,8 @@ def voxelize_cl(heatmaps_cl: torch.Tensor, J: int, packed_grids: torch.Tensor, g
 @voxelize_cl.register_fake
 def _(heatmaps_cl, J, packed_grids, grid_index, X, Y, Z, want_cube, want_xy):
     B = heatmaps_cl.shape[0]
-    return (heatmaps_cl.new_empty((B, J, X, Y, Z) if want_cube else (0,)),
-            heatmaps_cl.new_empty((B, J, X, Y) if want_xy else (0,)))
+    return (heatmaps_cl.new_empty((B, J, X, Y, Z) if want_cube else (0,), dtype=torch.float32),
+            heatmaps_cl.new_empty((B, J, X, Y) if want_xy else (0,), dtype=torch.float32))
 
 
 @_custom_op("fvp::voxelize_cl_cams", mutates_args=(), device_types="cuda")
@@ -313,9 +319,9 @@ def voxelize_cl_cams(heatmaps_cl: torch.Tensor, J: int, cams: torch.Tensor, grid
     im = ImageSpec(ori_max, img_w, img_h, W, H)
     outs = (_ptr(cube) if want_cube else None, _ptr(xy) if want_xy else None, _stream(hm))
     if X == bins[0]:
-        _lib.call("fvp_voxelize_cl_cams", _ptr(hm), cp, B, V, J, H, W, _ptr(cm), _ptr(gi), _ptr(rt), g, im, *outs)
+        _lib.call(_f16("fvp_voxelize_cl_cams", hm), _ptr(hm), cp, B, V, J, H, W, _ptr(cm), _ptr(gi), _ptr(rt), g, im, *outs)
     else:
-        _lib.call("fvp_voxelize_cl_cams_slab", _ptr(hm), cp, B, V, J, H, W, _ptr(cm), _ptr(gi), _ptr(rt), g, im,
+        _lib.call(_f16("fvp_voxelize_cl_cams_slab", hm), _ptr(hm), cp, B, V, J, H, W, _ptr(cm), _ptr(gi), _ptr(rt), g, im,
                   x0, x1, *outs)
     return cube, xy
 
@@ -325,8 +331,8 @@ def _(heatmaps_cl, J, cams, grid_index, resize_t, start, end, center, bins, ori_
       want_xy, x_begin=0, x_end=-1):
     B = heatmaps_cl.shape[0]
     _, _, X, Y, Z = _x_rows(bins, x_begin, x_end)
-    return (heatmaps_cl.new_empty((B, J, X, Y, Z) if want_cube else (0,)),
-            heatmaps_cl.new_empty((B, J, X, Y) if want_xy else (0,)))
+    return (heatmaps_cl.new_empty((B, J, X, Y, Z) if want_cube else (0,), dtype=torch.float32),
+            heatmaps_cl.new_empty((B, J, X, Y) if want_xy else (0,), dtype=torch.float32))
 
 
 # ---------------------------------------------------------------------------
@@ -440,13 +446,13 @@ def voxel_columns(heatmaps: torch.Tensor, cl_joints: int, packed_grids: Optional
     """columns[b,k,j,:] = cube[b,j,flat[b,k],:] of the cube voxelize (packed_grids)
     or voxelize_cams (cams) would produce, recomputed for the K winners only
     (fvp_voxel_columns; bit-identical).  heatmaps: planar [B,V,J,H,W] fp32/fp16
-    (cl_joints = 0) or channels-last [B,V,H,W,cp] fp32 with cl_joints = J."""
+    (cl_joints = 0) or channels-last [B,V,H,W,cp] fp32/fp16 with cl_joints = J."""
     if heatmaps.device.type != "cuda":
         raise _lib.FvpError(f"fvp: heatmaps must be on a HIP device, got {heatmaps.device}")
     if cl_joints:
         hm = _cl_input(heatmaps, cl_joints)
         B, V, H, W, cp = hm.shape
-        J, half, strides = cl_joints, False, (H * W * cp, 1, cp)
+        J, half, strides = cl_joints, hm.dtype == torch.float16, (H * W * cp, 1, cp)
     else:
         half = heatmaps.dtype == torch.float16
         hm = heatmaps.contiguous() if half else _dev_f32(heatmaps, "heatmaps")
@@ -597,7 +603,7 @@ def person_planes_cl(heatmaps_cl: torch.Tensor, J: int, fine_grid: torch.Tensor,
     offset = torch.empty((P, 3), dtype=torch.float32, device=hm.device)
     if P > 0:
         spec = PersonSpec(_i3(fine), _f3(scale), _f3(bias), _f3(whole_size), _f3(ind_size), _i3(bins))
-        _lib.call("fvp_person_planes_cl", _ptr(hm), cp, B, V, J, H, W, _ptr(fg), spec, _ptr(pc), _ptr(fo), P,
+        _lib.call(_f16("fvp_person_planes_cl", hm), _ptr(hm), cp, B, V, J, H, W, _ptr(fg), spec, _ptr(pc), _ptr(fo), P,
                   _ptr(cubes) if want_cubes else None, _ptr(planes) if want_planes else None, _ptr(offset),
                   _stream(hm))
     return cubes, planes, offset
@@ -607,9 +613,9 @@ def person_planes_cl(heatmaps_cl: torch.Tensor, J: int, fine_grid: torch.Tensor,
 def _(heatmaps_cl, J, fine_grid, proposals, frame_of, fine, scale, bias, whole_size, ind_size, bins, want_cubes,
       want_planes):
     P = proposals.shape[0]
-    return (heatmaps_cl.new_empty((P, J, bins[0], bins[1], bins[2]) if want_cubes else (0,)),
-            heatmaps_cl.new_empty((3 * P, J, bins[0], bins[1]) if want_planes else (0,)),
-            heatmaps_cl.new_empty((P, 3)))
+    return (heatmaps_cl.new_empty((P, J, bins[0], bins[1], bins[2]) if want_cubes else (0,), dtype=torch.float32),
+            heatmaps_cl.new_empty((3 * P, J, bins[0], bins[1]) if want_planes else (0,), dtype=torch.float32),
+            heatmaps_cl.new_empty((P, 3), dtype=torch.float32))
 
 
 @_custom_op("fvp::person_planes_cams", mutates_args=(), device_types="cuda")

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import geometry, ops
+from . import _lib, geometry, ops
 from .heatmaps import ChannelsLastHeatmaps, channels_last_of
 
 
@@ -127,6 +127,10 @@ class ProjectLayer(nn.Module):
         or fvp.heatmaps.ChannelsLastHeatmaps (read in place on the cached-grid path)."""
         cl = channels_last_of(heatmaps)
         if self._otf(heatmaps.shape[1]):
+            if cl is not None and cl.dtype == torch.float16:
+                # (no fp16 channels-last kernel projects the fine grid on the fly; never converted silently)
+                raise _lib.FvpError(f"fvp: the on-the-fly person path has no kernel for channels-last heatmaps of "
+                                    f"dtype {cl.dtype}: use the cached fine grid (on_the_fly = False), or fp32")
             if isinstance(heatmaps, ChannelsLastHeatmaps):
                 heatmaps = heatmaps.planar()
             seq = meta["seq"][index]

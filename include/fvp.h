@@ -171,6 +171,30 @@ int fvp_voxelize_cl_cams_slab(const float *heatmaps_cl, int cp, int B, int V, in
                               const fvp_grid_spec *grid, const fvp_image_spec *img, int x_begin, int x_end,
                               float *cube, float *xy, void *stream);
 
+/* The three entry points above on fp16 channels-last heatmaps, [B][V][H][W][cp]
+ * fp16 with cp % 8 == 0 and cp >= J, cp counted in fp16 elements (joints j < J
+ * in channels 0..J-1, the rest ignored), base pointer 16-B aligned.  The fp16
+ * taps are converted inside the fp32 fmas (exact), every fp32 operation after
+ * is the reference's, so the cube equals project_whole.py:119-168 (grid_sample
+ * per frame, mean over the cameras, clamp) run on the fp16-rounded heatmaps bit
+ * for bit -- the contract of the planar fp16 entry point, without its pixel-pair
+ * table: a 16-joint pixel is 32 B, one 16-B lane load carries 8 joints, a voxel
+ * takes 1 / 2 / 4 lanes for J <= 8 / 16 / 32 (more joints: slices of 32), so a
+ * wave's four tap loads serve twice the voxels of the fp32 layout.  No
+ * workspace, no layout pass, one launch per batch (per 32-joint slice).
+ * FVP_ERR_SHAPE: cp % 8 != 0, cp < J, J > FVP_MAX_JOINTS, a misaligned base
+ * pointer, or a camera image beyond 32-bit byte offsets (H*W*cp*2 >= 2^31). */
+int fvp_voxelize_cl_f16(const void *heatmaps_cl, int cp, int B, int V, int J, int H, int W,
+                        const float *packed_grids, const int32_t *grid_index, int X, int Y, int Z, float *cube,
+                        float *xy, void *stream);
+int fvp_voxelize_cl_cams_f16(const void *heatmaps_cl, int cp, int B, int V, int J, int H, int W, const float *cams,
+                             const int32_t *grid_index, const float *resize_t, const fvp_grid_spec *grid,
+                             const fvp_image_spec *img, float *cube, float *xy, void *stream);
+int fvp_voxelize_cl_cams_slab_f16(const void *heatmaps_cl, int cp, int B, int V, int J, int H, int W,
+                                  const float *cams, const int32_t *grid_index, const float *resize_t,
+                                  const fvp_grid_spec *grid, const fvp_image_spec *img, int x_begin, int x_end,
+                                  float *cube, float *xy, void *stream);
+
 /* Peak NMS + top-K on a [B,1,X,Y] map: 3x3 max-pool keep mask, top-K of the
  * masked map (value descending, flat index ascending on ties), and
  * get_index2D's (flat // X, flat % X) decode.
@@ -272,6 +296,14 @@ int fvp_person_planes_cams(const float *heatmaps, int B, int V, int J, int H, in
 int fvp_person_planes_cl(const float *heatmaps_cl, int cp, int B, int V, int J, int H, int W, const float *fine_grid,
                          const fvp_person_spec *spec, const float *proposals, const int32_t *frame_of, int P,
                          float *cubes, float *planes, float *offset, void *stream);
+/* The same on fp16 channels-last heatmaps (layout, cp and the FVP_ERR_SHAPE
+ * cases as fvp_voxelize_cl_f16): project_individual.py:222-293 and the planes of
+ * joint_localization_net.py:158-160 on the fp16-rounded heatmaps, bit for bit
+ * what fvp_person_planes_cl gives on their fp32 copy.  Cached fine grid only. */
+int fvp_person_planes_cl_f16(const void *heatmaps_cl, int cp, int B, int V, int J, int H, int W,
+                             const float *fine_grid, const fvp_person_spec *spec, const float *proposals,
+                             const int32_t *frame_of, int P, float *cubes, float *planes, float *offset,
+                             void *stream);
 
 /* xy / xz / yz max-projections of per-person cubes [P][J][S][S][S] into
  * planes [3P][J][S][S] (xy block first, then xz, then yz).
@@ -559,6 +591,12 @@ int fvp_weight_net(const float *features, int Nimg, int H, int W, const float *c
 /* NCHW [N][C][H][W] <-> NHWC [N][H][W][Cp] (Cp >= C, padding channels zero). */
 int fvp_nchw_to_nhwc(const float *in, int N, int C, int H, int W, int Cp, float *out, void *stream);
 int fvp_nhwc_to_nchw(const float *in, int N, int C, int H, int W, int Cp, float *out, void *stream);
+/* Planar [N][C][H][W] fp32 (in_half = 0) or fp16 (1) -> channels-last fp16
+ * [N][H][W][Cp], Cp % 8 == 0, Cp >= C, channels C..Cp-1 zero; fp32 values are
+ * rounded to nearest even, as Tensor.half() -- the layout fvp_voxelize_cl_f16
+ * reads, replacing heatmaps.half() plus a permute (the reference keeps the
+ * planar layout, lib/models/project_whole.py:119).  out 16-B aligned. */
+int fvp_nchw_to_nhwc_f16(const void *in, int in_half, int N, int C, int H, int W, int Cp, void *out, void *stream);
 
 /* Input heatmaps painted from 2-D keypoints, written channels-last in one
  * launch: what JointsDataset.generate_input_heatmap (lib/dataset/JointsDataset.py:
