@@ -180,7 +180,9 @@ def test_wino_conv_vs_torch(gpu_device, n, cin, cout, hw, res):
     20^2 / 40^2 maps), one and several 16-channel K steps, 32- and 64-column
     blocks (Cout padded to 32 / 64), the 8-wave xi-split blocks of small
     launches and the 4-wave blocks of large ones (fvp_conv3x3_wino_plan), BN
-    folded, the residual added before or after the ReLU: fp32 tolerance."""
+    folded, the residual added before or after the ReLU: fp32 tolerance.
+    (tests/test_gpu_wino_grids.py bounds the transforms' rounding elementwise,
+    against float64, on every tile grid and instantiation.)"""
     import torch.nn as nn
 
     from fvp import cnn, synthetic
