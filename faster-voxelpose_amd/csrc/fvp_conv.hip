@@ -28,6 +28,7 @@
 // The K dimension is walked in chunks of 16 (one (ky,kx) tap, 16 input
 // channels; with Cpi < 16 a chunk spans 16/Cpi taps) staged through LDS, the
 // next chunk's global loads issued before the current chunk's MFMAs.
+#include <climits>
 #include <type_traits>
 
 #include "fvp_layout.h"  // fvp_device.h, buffer descriptors (uniform_rsrc, kOOB)
@@ -1986,16 +1987,30 @@ static size_t conv_ws_bytes(int N, int Cpi, int KH, int KW, int Cpo, const ConvG
     return p.ks > 1 ? (size_t)conv_groups(g.mode) * p.ks * N * g.Hm * g.Wm * Ntot * sizeof(float) : 0;
 }
 
-// bf16 flags: FVP_CONV_BF16 (operands), FVP_CONV_BF16_IN / _OUT (activations stored as bf16;
-// the output's residuals likewise) -- the last two only with bf16 operands.
-static int conv_launch(const float *in, int N, int H, int W, int Cpi, const void *wpack, int KH, int KW, int Cpo,
-                       int Cpo_w, const float *scale, const float *shift, const float *res_pre,
-                       const float *res_post, int relu, const ConvGeom &g, float *out, int bf16, int algo, void *ws,
-                       size_t ws_bytes, void *stream) {
-    if (bf16 & ~(FVP_CONV_BF16 | FVP_CONV_BF16_IN | FVP_CONV_BF16_OUT | FVP_CONV_F32_KC)) return FVP_ERR_SHAPE;
-    if ((bf16 & (FVP_CONV_BF16_IN | FVP_CONV_BF16_OUT)) && !(bf16 & FVP_CONV_BF16)) return FVP_ERR_SHAPE;
-    if ((bf16 & FVP_CONV_F32_KC) && (bf16 & FVP_CONV_BF16)) return FVP_ERR_SHAPE;
-    if (!in || !wpack || !scale || !shift || !out) return FVP_ERR_NULL;
+// The one launch decision of a convolution: conv_launch switches on it, and
+// fvp_conv2d_ex_plan reports it (host only), so a test can state which kernel
+// instantiation a shape runs.
+struct ConvRoute {
+    int family;        // 1 conv_mfma_kernel, 2 conv_halo_kernel, 3 conv_bf16_kernel, 4 conv_dma_kernel
+    int BM, BN, KC;    // block tile and the K depth of one step
+    int var;           // per-tap PF (1, 2); halo KMAX (3, 7); bf16 kernel in_bf16 (0, 1); DMA waves (4, 8)
+    int ks;            // split-K factor used (1 = none)
+    int G;             // parity groups
+    long long blocks;  // blocks of the convolution's launch
+};
+
+static bool conv_flags_ok(int bf16) {
+    if (bf16 & ~(FVP_CONV_BF16 | FVP_CONV_BF16_IN | FVP_CONV_BF16_OUT | FVP_CONV_F32_KC)) return false;
+    if ((bf16 & (FVP_CONV_BF16_IN | FVP_CONV_BF16_OUT)) && !(bf16 & FVP_CONV_BF16)) return false;
+    if ((bf16 & FVP_CONV_F32_KC) && (bf16 & FVP_CONV_BF16)) return false;
+    return true;
+}
+
+// Validates the shape and picks the kernel.  ws_bytes: the split-K scratch at
+// hand (0 when the pointer is null).
+static int conv_route(int N, int H, int W, int Cpi, int KH, int KW, int Cpo, int Cpo_w, const ConvGeom &g, int bf16,
+                      int algo, size_t ws_bytes, ConvRoute &r) {
+    if (!conv_flags_ok(bf16)) return FVP_ERR_SHAPE;
     if (N <= 0 || Cpo <= 0 || Cpo % 16) return FVP_ERR_SHAPE;
     if (algo < FVP_CONV_AUTO || algo > FVP_CONV_PER_TAP_NOSPLIT) return FVP_ERR_SHAPE;
     const int Ntot = conv_cols(g.mode, Cpo);
@@ -2004,51 +2019,124 @@ static int conv_launch(const float *in, int N, int H, int W, int Cpi, const void
     if ((long long)N * g.Ho * g.Wo * Cpo > 0x7fffffffLL * 4 || (long long)N * H * W * Cpi > 0x7fffffffLL * 4)
         return FVP_ERR_SHAPE;
     const int G = conv_groups(g.mode);
-    fvp::ConvArgs a{in, reinterpret_cast<const float *>(wpack), scale, shift, res_pre, res_post, out, N, H, W, Cpi,
-                    KH, KW, Cpo, Cpo_w, relu, g.mode, g.Hm, g.Wm, g.sy, g.sx, g.py, g.px, 1, nullptr,
-                    (bf16 & FVP_CONV_BF16_IN) ? 1 : 0, (bf16 & FVP_CONV_BF16_OUT) ? 1 : 0};
-    hipStream_t st = (hipStream_t)stream;
+    r = ConvRoute{0, 0, 0, 0, 0, 1, G, 0};
+    auto grid = [&] { r.blocks = G * ((M + r.BM - 1) / r.BM) * ((Ntot + r.BN - 1) / r.BN); };
     // LDS-DMA kernel: one K step = one tap x a 128-B (or 64-B) row of channels
     const int es = (bf16 & FVP_CONV_BF16) ? 2 : 4;
     const long long Kd = (long long)KH * KW * Cpi;
     const bool fits = (long long)N * H * W * Cpi * es < (1LL << 31) && (long long)Cpo_w * Kd * es < (1LL << 31) &&
                       KH * KW <= 32 && M < (1 << 24);  // 32-bit buffer offsets, tap masks, row decode
-    auto dma = [&](auto f32) {
-        constexpr bool F = decltype(f32)::value;
-        constexpr int E = F ? 4 : 2;
+    auto dma = [&](int E) {  // E: operand bytes
         // 32-column tiles (4 waves of 32 x 32) for the <= 32-channel layers, 128-B rows only.
         // fp32 takes 64-column tiles where bf16 takes 128: 4 waves and 48 KB of LDS per
         // block, 3 blocks per CU instead of 2 of 8 waves -- PoseResNet-50 fp32 layers
         // 31.02 -> 30.53 ms (3x3/s2 512->512 at 32 x 60: 0.85 -> 0.73 ms, the 1x1
         // expand layers 3-7 %; profiles/round6/dma_bn64/)
-        const int BN = Ntot > 64 ? (F ? 64 : 128) : (Ntot > 32 || Cpi * E % 128) ? 64 : 32;
-        const dim3 gr((unsigned)((M + 127) / 128), (unsigned)((Ntot + BN - 1) / BN), (unsigned)G);
-        if (BN == 32) {
-            hipLaunchKernelGGL((fvp::conv_dma_kernel<32, 128 / E, 4, F>), gr, dim3(256), 0, st, a, wpack);
-        } else if (Cpi * E % 128 == 0) {  // 128-B rows
-            if (BN == 128) hipLaunchKernelGGL((fvp::conv_dma_kernel<128, 128 / E, 8, F>), gr, dim3(512), 0, st, a, wpack);
-            else hipLaunchKernelGGL((fvp::conv_dma_kernel<64, 128 / E, 4, F>), gr, dim3(256), 0, st, a, wpack);
-        } else {  // 64-B rows (32 bf16 / 16 fp32 channels)
-            if (BN == 128) hipLaunchKernelGGL((fvp::conv_dma_kernel<128, 64 / E, 8, F>), gr, dim3(512), 0, st, a, wpack);
-            else hipLaunchKernelGGL((fvp::conv_dma_kernel<64, 64 / E, 4, F>), gr, dim3(256), 0, st, a, wpack);
-        }
-        return (int)hipGetLastError();
+        r.family = 4;
+        r.BM = 128;
+        r.BN = Ntot > 64 ? (E == 4 ? 64 : 128) : (Ntot > 32 || Cpi * E % 128) ? 64 : 32;
+        r.KC = (r.BN == 32 || Cpi * E % 128 == 0 ? 128 : 64) / E;  // 128-B rows, else 64-B (32 bf16 / 16 fp32 channels)
+        r.var = r.BN == 128 ? 8 : 4;
+        grid();
     };
     if (bf16 & FVP_CONV_F32_KC) {  // fp32 operands, weights [G][Cpo_w][Krows]: the DMA kernel or nothing
         if (Cpi % 16 || !fits) return FVP_ERR_SHAPE;
-        return dma(std::true_type{});
+        dma(4);
+        return FVP_OK;
     }
     if (bf16) {  // chunks of one tap x 16 / 32 channels (or several taps of a 4/8/12-channel input), no split
-        if (Cpi % 16 && (bf16 & FVP_CONV_BF16_IN)) return FVP_ERR_SHAPE;
-        const __bf16 *wb = reinterpret_cast<const __bf16 *>(wpack);
+        const int in_bf16 = (bf16 & FVP_CONV_BF16_IN) ? 1 : 0;
+        if (Cpi % 16 && in_bf16) return FVP_ERR_SHAPE;
         // LDS-DMA kernel (measured against the register-staged one on ResNet-50
         // at 40 x 960 x 512: 3x3 64->64 0.21 -> 0.15 ms, deconv 256->256 at 64x120
         // 1.21 -> 0.76 ms, 1x1 256->1024 at 32x60 0.15 -> 0.11 ms; the 64->256
         // expand layers at 128x240 tie at 0.31 ms, output bound)
-        if (a.in_bf16 && Cpi % 32 == 0 && algo != FVP_CONV_PER_TAP_NOSPLIT && fits) return dma(std::false_type{});
+        if (in_bf16 && Cpi % 32 == 0 && algo != FVP_CONV_PER_TAP_NOSPLIT && fits) {
+            dma(2);
+            return FVP_OK;
+        }
+        const long long b128 = G * ((M + 127) / 128) * ((Ntot + 63) / 64);
+        r.family = 3;
+        r.BM = Ntot <= 32 || b128 >= 512 ? 128 : 64;
+        r.BN = Ntot <= 32 ? 32 : 64;
+        r.KC = Cpi % 32 == 0 ? 32 : 16;
+        r.var = in_bf16;
+        grid();
+        return FVP_OK;
+    }
+    const ConvPlan p = conv_plan(N, Cpi, KH, KW, Ntot, g, algo);
+    if (p.halo) {
+        r.family = 2;
+        r.BM = kTileBM[p.halo];
+        r.BN = kTileBN[p.halo];
+        r.KC = 16;
+        r.var = KH <= 3 && KW <= 3 ? 3 : 7;
+        r.blocks = (long long)N * ((W + 15) / 16) * ((H + r.BM / 16 - 1) / (r.BM / 16)) * ((Ntot + r.BN - 1) / r.BN);
+        return FVP_OK;
+    }
+    // Measured per layer on CenterNet at 8 frames (rocprofv3 kernel traces,
+    // profiles/round3/centernet_trace): 32-deep K chunks on the 64 x 32 tile
+    // (3x3 32->32 at 80x80: 24-26 -> 21-24 us) and two chunks in flight on the
+    // 64 x 16 tile (7x7 16->16 front: 46 -> 42.5 us); the same changes on the
+    // 32 x 64 tile, a padded B pitch and an LDS-free wave-per-tile kernel were
+    // neutral or slower (DESIGN.md section 7).
+    r.family = 1;
+    r.BM = kTileBM[p.tile];
+    r.BN = kTileBN[p.tile];
+    r.KC = p.tile == 4 && Cpi % 32 == 0 ? 32 : 16;  // (a 32-deep chunk = 32 channels of one tap)
+    r.var = p.tile == 2 ? 2 : 1;
+    r.ks = p.ks;
+    if (r.ks > 1 && ws_bytes < (size_t)G * r.ks * M * Ntot * sizeof(float)) r.ks = 1;  // no scratch: no split
+    grid();
+    r.blocks *= r.ks;
+    return FVP_OK;
+}
+
+// bf16 flags: FVP_CONV_BF16 (operands), FVP_CONV_BF16_IN / _OUT (activations stored as bf16;
+// the output's residuals likewise) -- the last two only with bf16 operands.
+// Which kernel runs is conv_route's decision alone (fvp_conv2d_ex_plan reports it;
+// tests/test_conv_route_model.py pins it against an independent model, tests/conv_cases.py
+// holds a case for every instantiation below).
+static int conv_launch(const float *in, int N, int H, int W, int Cpi, const void *wpack, int KH, int KW, int Cpo,
+                       int Cpo_w, const float *scale, const float *shift, const float *res_pre,
+                       const float *res_post, int relu, const ConvGeom &g, float *out, int bf16, int algo, void *ws,
+                       size_t ws_bytes, void *stream) {
+    if (!conv_flags_ok(bf16)) return FVP_ERR_SHAPE;
+    if (!in || !wpack || !scale || !shift || !out) return FVP_ERR_NULL;
+    ConvRoute r;
+    const int rs = conv_route(N, H, W, Cpi, KH, KW, Cpo, Cpo_w, g, bf16, algo, ws ? ws_bytes : 0, r);
+    if (rs != FVP_OK) return rs;
+    const int Ntot = conv_cols(g.mode, Cpo);
+    const long long M = (long long)N * g.Hm * g.Wm;
+    const int G = r.G;
+    fvp::ConvArgs a{in, reinterpret_cast<const float *>(wpack), scale, shift, res_pre, res_post, out, N, H, W, Cpi,
+                    KH, KW, Cpo, Cpo_w, relu, g.mode, g.Hm, g.Wm, g.sy, g.sx, g.py, g.px, 1, nullptr,
+                    (bf16 & FVP_CONV_BF16_IN) ? 1 : 0, (bf16 & FVP_CONV_BF16_OUT) ? 1 : 0};
+    hipStream_t st = (hipStream_t)stream;
+    const int tile = r.BM * 1000 + r.BN;  // the block tile as one switch value
+    // GEMM grid of the per-tap, bf16 and DMA kernels: row tiles x column tiles x (groups x split-K)
+    const dim3 gr((unsigned)((M + r.BM - 1) / r.BM), (unsigned)((Ntot + r.BN - 1) / r.BN), (unsigned)(G * r.ks));
+    if (r.family == 4) {
+#define FVP_DMA(BN, BK, NW, F)                                                                                   \
+    hipLaunchKernelGGL((fvp::conv_dma_kernel<BN, BK, NW, F>), gr, dim3(NW * 64), 0, st, a, wpack)
+        if (bf16 & FVP_CONV_F32_KC) switch (r.BN * 1000 + r.KC) {
+            case 32032: FVP_DMA(32, 32, 4, true); break;
+            case 64032: FVP_DMA(64, 32, 4, true); break;
+            default: FVP_DMA(64, 16, 4, true); break;
+        } else switch (r.BN * 1000 + r.KC) {
+            case 32064: FVP_DMA(32, 64, 4, false); break;
+            case 64064: FVP_DMA(64, 64, 4, false); break;
+            case 128064: FVP_DMA(128, 64, 8, false); break;
+            case 64032: FVP_DMA(64, 32, 4, false); break;
+            default: FVP_DMA(128, 32, 8, false); break;
+        }
+#undef FVP_DMA
+        return (int)hipGetLastError();
+    }
+    if (r.family == 3) {
+        const __bf16 *wb = reinterpret_cast<const __bf16 *>(wpack);
 #define FVP_CONVB(BM, BN, WR, KC)                                                                               \
     do {                                                                                                          \
-        const dim3 gr((unsigned)((M + BM - 1) / BM), (unsigned)((Ntot + BN - 1) / BN), (unsigned)G);             \
         if (a.in_bf16)                                                                                            \
             hipLaunchKernelGGL((fvp::conv_bf16_kernel<fvp::TileB<BM, BN, WR, KC>, true>), gr, dim3(256), 0, st, a, \
                                wb);                                                                               \
@@ -2056,78 +2144,62 @@ static int conv_launch(const float *in, int N, int H, int W, int Cpi, const void
             hipLaunchKernelGGL((fvp::conv_bf16_kernel<fvp::TileB<BM, BN, WR, KC>, false>), gr, dim3(256), 0, st,  \
                                a, wb);                                                                            \
     } while (0)
-        const bool k32 = Cpi % 32 == 0;
-        const long long b128 = G * ((M + 127) / 128) * ((Ntot + 63) / 64);
-        if (Ntot <= 32) {
-            if (k32) FVP_CONVB(128, 32, 4, 32); else FVP_CONVB(128, 32, 4, 16);
-        } else if (b128 >= 512) {
-            if (k32) FVP_CONVB(128, 64, 2, 32); else FVP_CONVB(128, 64, 2, 16);
-        } else {
-            if (k32) FVP_CONVB(64, 64, 2, 32); else FVP_CONVB(64, 64, 2, 16);
+        const bool k32 = r.KC == 32;
+        switch (tile) {
+            case 128032:
+                if (k32) FVP_CONVB(128, 32, 4, 32); else FVP_CONVB(128, 32, 4, 16);
+                break;
+            case 128064:
+                if (k32) FVP_CONVB(128, 64, 2, 32); else FVP_CONVB(128, 64, 2, 16);
+                break;
+            default:
+                if (k32) FVP_CONVB(64, 64, 2, 32); else FVP_CONVB(64, 64, 2, 16);
+                break;
         }
 #undef FVP_CONVB
         return (int)hipGetLastError();
     }
-    ConvPlan p = conv_plan(N, Cpi, KH, KW, Ntot, g, algo);
-    if (p.ks > 1 && (!ws || ws_bytes < (size_t)G * p.ks * M * Ntot * sizeof(float))) p.ks = 1;  // no scratch: no split
-    if (p.ks > 1) {
-        a.part = reinterpret_cast<float *>(ws);
-        a.ks = p.ks;
-    }
-    if (p.halo) {
+    if (r.family == 2) {
         const int tx = (W + 15) / 16;
 #define FVP_HALO(TL)                                                                                              \
     do {                                                                                                          \
         const int ty = (H + fvp::TL::BM / 16 - 1) / (fvp::TL::BM / 16);                                           \
-        const dim3 gr((unsigned)((long long)N * tx * ty), (unsigned)((Ntot + fvp::TL::BN - 1) / fvp::TL::BN));    \
-        if (KH <= 3 && KW <= 3)                                                                                   \
-            hipLaunchKernelGGL((fvp::conv_halo_kernel<fvp::TL, 3>), gr, dim3(256), 0, st, a, tx, ty);             \
+        const dim3 gh((unsigned)((long long)N * tx * ty), (unsigned)((Ntot + fvp::TL::BN - 1) / fvp::TL::BN));    \
+        if (r.var == 3)                                                                                           \
+            hipLaunchKernelGGL((fvp::conv_halo_kernel<fvp::TL, 3>), gh, dim3(256), 0, st, a, tx, ty);             \
         else                                                                                                      \
-            hipLaunchKernelGGL((fvp::conv_halo_kernel<fvp::TL, 7>), gr, dim3(256), 0, st, a, tx, ty);             \
+            hipLaunchKernelGGL((fvp::conv_halo_kernel<fvp::TL, 7>), gh, dim3(256), 0, st, a, tx, ty);             \
     } while (0)
-        switch (p.halo) {
-            case 1: FVP_HALO(TileN16); break;
-            case 2: FVP_HALO(TileN16s); break;
-            case 3: FVP_HALO(TileN32); break;
-            case 4: FVP_HALO(TileN32s); break;
-            case 5: FVP_HALO(TileN64); break;
-            case 6: FVP_HALO(TileN64m); break;
+        switch (tile) {
+            case 256016: FVP_HALO(TileN16); break;
+            case 64016: FVP_HALO(TileN16s); break;
+            case 128032: FVP_HALO(TileN32); break;
+            case 64032: FVP_HALO(TileN32s); break;
+            case 128064: FVP_HALO(TileN64); break;
+            case 64064: FVP_HALO(TileN64m); break;
             default: FVP_HALO(TileN64s); break;
         }
 #undef FVP_HALO
         return (int)hipGetLastError();
     }
-#define FVP_CONV(TL)                                                                                              \
-    hipLaunchKernelGGL((fvp::conv_mfma_kernel<fvp::TL>),                                                          \
-                       dim3((unsigned)((M + fvp::TL::BM - 1) / fvp::TL::BM),                                      \
-                            (unsigned)((Ntot + fvp::TL::BN - 1) / fvp::TL::BN), (unsigned)(G * p.ks)),            \
-                       dim3(256), 0, st, a)
-#define FVP_CONV2(TL)                                                                                             \
-    hipLaunchKernelGGL((fvp::conv_mfma_kernel<fvp::TL, 2>),                                                       \
-                       dim3((unsigned)((M + fvp::TL::BM - 1) / fvp::TL::BM),                                      \
-                            (unsigned)((Ntot + fvp::TL::BN - 1) / fvp::TL::BN), (unsigned)(G * p.ks)),            \
-                       dim3(256), 0, st, a)
-    // Measured per layer on CenterNet at 8 frames (rocprofv3 kernel traces,
-    // profiles/round3/centernet_trace): 32-deep K chunks on the 64 x 32 tile
-    // (3x3 32->32 at 80x80: 24-26 -> 21-24 us) and two chunks in flight on the
-    // 64 x 16 tile (7x7 16->16 front: 46 -> 42.5 us); the same changes on the
-    // 32 x 64 tile, a padded B pitch and an LDS-free wave-per-tile kernel were
-    // neutral or slower (DESIGN.md section 7).
-    if (p.tile == 4 && Cpi % 32 == 0) {  // (a 32-deep chunk = 32 channels of one tap)
-        FVP_CONV(TileN32sK);
-    } else if (p.tile == 2) {
-        FVP_CONV2(TileN16s);
-    } else switch (p.tile) {  // (tile 2 took the branch above)
-        case 1: FVP_CONV(TileN16); break;
-        case 3: FVP_CONV(TileN32); break;
-        case 4: FVP_CONV(TileN32s); break;
-        case 5: FVP_CONV(TileN64); break;
-        case 6: FVP_CONV(TileN64m); break;
+    if (r.ks > 1) {
+        a.part = reinterpret_cast<float *>(ws);
+        a.ks = r.ks;
+    }
+#define FVP_CONV(TL) hipLaunchKernelGGL((fvp::conv_mfma_kernel<fvp::TL>), gr, dim3(256), 0, st, a)
+    switch (tile) {
+        case 256016: FVP_CONV(TileN16); break;
+        case 64016: hipLaunchKernelGGL((fvp::conv_mfma_kernel<fvp::TileN16s, 2>), gr, dim3(256), 0, st, a); break;
+        case 128032: FVP_CONV(TileN32); break;
+        case 64032:
+            if (r.KC == 32) FVP_CONV(TileN32sK); else FVP_CONV(TileN32s);
+            break;
+        case 128064: FVP_CONV(TileN64); break;
+        case 64064: FVP_CONV(TileN64m); break;
         default: FVP_CONV(TileN64s); break;
     }
 #undef FVP_CONV
-#undef FVP_CONV2
-    if (p.ks > 1) {
+    if (r.ks > 1) {
         const long long tot = G * M * Ntot;
         hipLaunchKernelGGL(fvp::conv_splitk_reduce, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, a, (int)M,
                            Ntot);
@@ -2199,6 +2271,22 @@ extern "C" size_t fvp_conv2d_ex_workspace_bytes(int N, int H, int W, int Cpi, in
     if (N <= 0 || Cpo <= 0 || Cpo % 16 || algo < FVP_CONV_AUTO || algo > FVP_CONV_PER_TAP_NOSPLIT) return 0;
     if (fvp::conv_geom(H, W, Cpi, KH, KW, mode, sy, sx, py, px, g) != FVP_OK) return 0;
     return fvp::conv_ws_bytes(N, Cpi, KH, KW, Cpo, g, algo);
+}
+
+extern "C" int fvp_conv2d_ex_plan(int N, int H, int W, int Cpi, int KH, int KW, int Cpo, int mode, int sy, int sx,
+                                  int py, int px, int bf16, int algo, size_t workspace_bytes, int *plan) {
+    if (!plan) return FVP_ERR_NULL;
+    fvp::ConvGeom g;
+    const int st = fvp::conv_geom(H, W, Cpi, KH, KW, mode, sy, sx, py, px, g);
+    if (st != FVP_OK) return st;
+    fvp::ConvRoute r;
+    // (Cpo_w as fvp/cnn.py packs the weights: the GEMM columns rounded up to 128)
+    const int Cpo_w = Cpo > 0 && Cpo <= (1 << 24) ? (fvp::conv_cols(g.mode, Cpo) + 127) / 128 * 128 : 0;
+    const int rs = fvp::conv_route(N, H, W, Cpi, KH, KW, Cpo, Cpo_w, g, bf16, algo, workspace_bytes, r);
+    if (rs != FVP_OK) return rs;
+    const int v[8] = {r.family, r.BM, r.BN, r.KC, r.var, r.ks, r.G, r.blocks > INT_MAX ? INT_MAX : (int)r.blocks};
+    for (int i = 0; i < 8; ++i) plan[i] = v[i];
+    return FVP_OK;
 }
 
 extern "C" int fvp_conv2d_nhwc_ex(const float *in, int N, int H, int W, int Cpi, const void *wpack, int KH, int KW,

@@ -103,6 +103,7 @@ SIGNATURES = {
                            c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                            c_void_p, c_void_p, ctypes.c_size_t, c_void_p],
     "fvp_conv2d_ex_workspace_bytes": [c_int] * 13,
+    "fvp_conv2d_ex_plan": [c_int] * 14 + [ctypes.c_size_t, ctypes.POINTER(c_int)],
     "fvp_conv2d_geom": [c_int] * 10 + [ctypes.POINTER(c_int)],
     "fvp_maxpool_pad_nhwc": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
     "fvp_conv1d_net_lds_bytes": [c_int, c_int, c_int, c_int],

@@ -58,7 +58,10 @@ _CUS = {}
 
 
 def _cus(dev: torch.device) -> int:
-    """Compute units of a device (cached)."""
+    """Compute units of a device (cached); off the GPU (conv_route's host-side queries) the
+    MI355X's 256."""
+    if torch.device(dev).type != "cuda":
+        return 256
     if dev not in _CUS:
         _CUS[dev] = torch.cuda.get_device_properties(dev).multi_processor_count
     return _CUS[dev]
@@ -325,6 +328,32 @@ class ConvLayer:
         Ho, Wo = self.out_hw(x.H, x.W)
         rows = x.N * (x.H * x.W if self.mode else Ho * Wo)  # GEMM rows (row grid) per parity group
         return 2 * rows * self.G * self.nq * self.Cout * self.Cin * self.KH * self.KW
+
+
+def conv_route(layer: ConvLayer, N: int, H: int, W: int, in_bf16: bool = False, residual: bool = False) -> tuple:
+    """The launch ``layer`` makes for an [N, H, W, Cpi] input (host only, no GPU work):
+    fvp_conv2d_ex_plan's (family, BM, BN, K depth, variant, split-K, groups, blocks) with
+    the flags, algo and workspace size ConvLayer.__call__ passes -- or ("wino",) /
+    ("wino_dc",) / ("blas",) where it runs Winograd or the library GEMM instead.
+    in_bf16: the input is stored as bf16; residual: the call has a residual (no library GEMM)."""
+    import types
+
+    dev = layer.wpack.device
+    dt = torch.bfloat16 if in_bf16 and layer.bf16 and layer.Cpi % 16 == 0 else torch.float32
+    x = types.SimpleNamespace(N=N, H=H, W=W, Cp=layer.Cpi, C=layer.Cin, t=types.SimpleNamespace(
+        dtype=dt, device=dev, is_contiguous=lambda: True))
+    if layer._blas(x, True, residual or None, None, x.t, False):
+        return ("blas",)
+    nws, kind = layer._plan(x)
+    if isinstance(kind, str):
+        return (kind,)
+    flags = FVP_CONV_F32_KC if kind else 0
+    if layer.bf16:
+        flags = 1 | (2 if dt == torch.bfloat16 else 0) | (4 if layer.act_bf16 else 0)
+    plan = (ctypes.c_int * 8)()
+    _lib.check(_lib.load().fvp_conv2d_ex_plan(N, H, W, layer.Cpi, layer.KH, layer.KW, layer.Cpo, *layer.geom(), flags,
+                                              layer._abi_algo(), nws, plan), "fvp_conv2d_ex_plan")
+    return tuple(plan)
 
 
 _WINO_G = ((1.0, 0.0, 0.0), (0.5, 0.5, 0.5), (0.5, -0.5, 0.5), (0.0, 0.0, 1.0))

@@ -450,6 +450,21 @@ int fvp_conv2d_nhwc_ex(const float *in, int N, int H, int W, int Cpi, const void
 #define FVP_CONV_F32_KC 8
 size_t fvp_conv2d_ex_workspace_bytes(int N, int H, int W, int Cpi, int KH, int KW, int Cpo, int mode, int sy,
                                      int sx, int py, int px, int algo);
+/* The launch fvp_conv2d_nhwc_ex makes for these arguments (host only, no GPU
+ * call; the launcher itself switches on the same decision).  bf16: the flags
+ * above; workspace_bytes: the split-K scratch the caller would pass (0: none).
+ * Returns the status fvp_conv2d_nhwc_ex would return with non-NULL pointers and
+ * Cpo_w = the GEMM columns rounded up to 128.  plan[0..7] =
+ *   0  kernel family: 1 conv_mfma_kernel (per tap), 2 conv_halo_kernel,
+ *      3 conv_bf16_kernel (register staged), 4 conv_dma_kernel (LDS-DMA)
+ *   1  BM, 2  BN (block tile: GEMM rows x columns), 3  K depth of one step
+ *   4  variant: per-tap chunks in flight (1, 2); halo KMAX (3, 7); bf16
+ *      kernel: input stored as bf16 (0, 1); DMA kernel: waves per block (4, 8)
+ *   5  split-K factor used (1: none, also when workspace_bytes is too small)
+ *   6  parity groups (4 for mode 3, else 1)
+ *   7  blocks of the convolution's launch (at most INT_MAX) */
+int fvp_conv2d_ex_plan(int N, int H, int W, int Cpi, int KH, int KW, int Cpo, int mode, int sy, int sx, int py,
+                       int px, int bf16, int algo, size_t workspace_bytes, int *plan);
 /* 3x3 stride-1 padding-1 Conv2d (cnns_2d.py:12-64 Basic2DBlock / Res2DBlock
  * 3x3 layers; resnet.py:60-95 Bottleneck conv2 at stride 1) by Winograd
  * F(2x2, 3x3) on the fp32 matrix cores, with the epilogue of

@@ -107,6 +107,29 @@ def test_wino_plan(shape, want):
     assert cnn.wino_plan(*shape) == want
 
 
+@pytest.mark.parametrize("args, want", [
+    # (N, H, W, Cpi, KH, KW, Cpo, mode, sy, sx, py, px, flags, algo, workspace bytes)
+    ((33, 63, 63, 16, 3, 3, 16, 0, 1, 1, 1, 1, 0, 2, 0), (2, 256, 16, 16, 3, 1, 1, 528)),       # halo, >= 512 blocks
+    ((31, 63, 63, 16, 3, 3, 16, 0, 1, 1, 1, 1, 0, 2, 0), (2, 64, 16, 16, 3, 1, 1, 1984)),       # 496 of 256 x 16: small
+    ((2, 5, 5, 32, 3, 3, 32, 0, 1, 1, 1, 1, 0, 1, 4 * 50 * 32 * 4), (1, 64, 32, 32, 1, 4, 1, 4)),  # split-K 4
+    ((2, 5, 5, 32, 3, 3, 32, 0, 1, 1, 1, 1, 0, 1, 4 * 50 * 32 * 4 - 1), (1, 64, 32, 32, 1, 1, 1, 1)),  # short scratch
+    ((8, 20, 20, 128, 2, 2, 128, 3, 0, 0, 0, 0, 3, 0, 0), (4, 128, 128, 64, 8, 1, 4, 100)),     # bf16 deconv: LDS-DMA
+    ((8, 20, 20, 128, 2, 2, 128, 3, 0, 0, 0, 0, 3, 3, 0), (3, 64, 64, 32, 1, 1, 4, 400)),     # NOSPLIT: register staged
+    ((8, 20, 20, 16, 3, 3, 64, 0, 2, 2, 1, 1, 8, 0, 0), (4, 128, 64, 16, 4, 1, 1, 7)),         # fp32 LDS-DMA, 64-B rows
+])
+def test_conv2d_ex_plan(args, want):
+    """fvp_conv2d_ex_plan (host only): family, BM, BN, K depth, variant, split-K, groups, blocks
+    -- the decision fvp_conv2d_nhwc_ex's launcher switches on (tests/test_conv_route_model.py
+    sweeps it against an independent model of the rules)."""
+    import ctypes
+
+    from fvp import _lib
+
+    plan = (ctypes.c_int * 8)()
+    assert _lib.load().fvp_conv2d_ex_plan(*args, plan) == 0
+    assert tuple(plan) == want
+
+
 def test_ops_refuse_cpu_tensors():
     from fvp import ops  # noqa: F401  (registers torch.ops.fvp.*)
 

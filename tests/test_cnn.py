@@ -269,7 +269,13 @@ def test_transposed_conv_and_pool_vs_torch(gpu_device):
 
 @pytest.mark.gpu
 def test_fvp_cnn_large_batch_tiles_vs_torch(gpu_device, conv_kernel):
-    """Enough images that every layer takes the large tiles (>= 2 blocks per CU)."""
+    """24 images: the 32-column layers at 64 x 64 take the large 128 x 32 tile (768 blocks) and no
+    layer splits K -- but not every layer takes a large tile: the 64-column layers at 32 x 32 and
+    16 x 16 stay on 32 x 64 (384 blocks of 64 x 64 at most; 64 x 64 only for the last upsampling),
+    the 16-column 7x7 front on 64 x 16 (384 blocks of 256 x 16 < 512, per-tap and halo alike), so
+    neither 256 x 16 tile and no 128 x 64 tile runs here (fvp.cnn.conv_route; every tile of every
+    kernel: tests/test_gpu_conv_routes.py).  The routes taken are asserted."""
+    from fvp import cnn
     from fvp.cnn import FvpCNN
 
     p2p, cn, _, _ = _nets()
@@ -277,8 +283,26 @@ def test_fvp_cnn_large_batch_tiles_vs_torch(gpu_device, conv_kernel):
     x = torch.rand((24, 15, 64, 64), generator=torch.Generator().manual_seed(5)).to(gpu_device)
     with torch.no_grad():
         ref = p2p(x)
-    got = FvpCNN(p2p, algo=conv_kernel)(x)
+    routes, call = set(), cnn.ConvLayer.__call__
+
+    def recording(self, a, relu, res_pre=None, res_post=None, out=None, pool=False):
+        routes.add(cnn.conv_route(self, a.N, a.H, a.W, residual=res_pre is not None or res_post is not None)[:6])
+        return call(self, a, relu, res_pre, res_post, out, pool)
+
+    cnn.ConvLayer.__call__ = recording
+    try:
+        got = FvpCNN(p2p, algo=conv_kernel)(x)
+    finally:
+        cnn.ConvLayer.__call__ = call
     _close(got.cpu().numpy(), ref.cpu().numpy(), "P2PNet, 24 images")
+    # (family, BM, BN, K depth, variant, split-K) of fvp_conv2d_ex_plan
+    front, n32, n64, up = (1, 64, 16, 16, 2, 1), (1, 128, 32, 16, 1, 1), (1, 32, 64, 16, 1, 1), (1, 64, 64, 16, 1, 1)
+    pertap = {front, n32, n64, up}
+    assert routes == {
+        cnn.CONV_HALO: {(2, 64, 16, 16, 7, 1), n32, (2, 128, 32, 16, 3, 1), n64, (2, 32, 64, 16, 3, 1), up},
+        cnn.CONV_PER_TAP: pertap, cnn.CONV_PER_TAP_NOSPLIT: pertap,
+        cnn.CONV_DMA: {front, (4, 128, 64, 16, 4, 1), (4, 128, 32, 32, 4, 1), (4, 128, 64, 32, 4, 1)},
+        cnn.CONV_WINO: pertap | {("wino",)}}[conv_kernel], sorted(routes, key=str)
 
 
 @pytest.mark.gpu
