@@ -19,10 +19,20 @@
 // once (padding channels and uncovered pixels as 0.0f): no memset, no atomics
 // on global memory, and max is order-free, so the output is deterministic.
 //
+// fp16 output (fvp_render_keypoints_f16, the layout fvp_voxelize_cl_f16 reads):
+// the same kernel with JPL = 8 joints per lane instead of 4.  A lane owns 8
+// channels of a pixel, a channel group is 8 channels with up to 8 P kept
+// records, and the lane converts each channel's fp32 maximum once, to nearest
+// even, and stores one 16-B piece -- still 1 KiB per wave store.  Rounding is
+// monotone, so max-then-round equals the fp32 render followed by Tensor.half()
+// bit for bit.
+//
 // The per-pixel value is fp32: expf(-(dx^2 + dy^2) * (float)(1 / (2 sigma^2)))
 // with the integer offsets from the window's centre pixel ul + floor(size / 2)
 // (which is often mu - 1, not mu: the reference's Gaussian sits on its patch).
 #include <math.h>
+
+#include <type_traits>
 
 #include "fvp_device.h"
 
@@ -52,7 +62,7 @@ struct RenderArgs {
     const void *joints;
     const int *count;
     const unsigned char *vis;
-    float *out;
+    void *out;  // fp32 (JPL 4) or fp16 (JPL 8)
     double stride_x, stride_y, sigma;
     int joints_f64, P, J, H, W, tiles_x, bands;
 };
@@ -64,16 +74,30 @@ __device__ __forceinline__ int trunc_int(double v) {
     return (int)fmin(fmax(v, -1073741824.0), 1073741824.0);
 }
 
-template <int CP>
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+
+// A lane's running maxima: channels 0..3 of its group, and 4..7 with 8 joints per lane.
+template <int JPL>
+struct RenderAcc {
+    float4 lo;
+};
+template <>
+struct RenderAcc<8> {
+    float4 lo, hi;
+};
+
+// JPL: joints (channels) per lane = per 16-B store: 4 fp32 or 8 fp16.
+template <int CP, int JPL>
 __global__ __launch_bounds__(kRenderThreads) void render_keypoints_kernel(const RenderArgs a) {
-    constexpr int QP = CP / 4;                // channel groups (float4) per pixel
+    constexpr int QP = CP / JPL;              // channel groups (one 16-B piece) per pixel
     constexpr int PPP = kRenderThreads / QP;  // pixels per pass
     constexpr int PASSES = kTileW * kBandH / PPP;
+    constexpr int SH = JPL == 4 ? 2 : 3;  // log2 JPL
     extern __shared__ double2 render_lds[];
     // kept records per tile and channel group; three sets in turn, so that one barrier per tile orders
     // a set's reset, its fill and its readers
     __shared__ int kept_n[3][QP];
-    __shared__ unsigned short kept[3][QP][kMaxRenderP * 4];
+    __shared__ unsigned short kept[3][QP][kMaxRenderP * JPL];  // id = record * JPL + channel in group < 2^13
     __shared__ int band_n;
 
     const int tid = threadIdx.x;
@@ -165,15 +189,16 @@ __global__ __launch_bounds__(kRenderThreads) void render_keypoints_kernel(const 
 
     const int nband = band_n;
     const int grp = tid % QP, pix = tid / QP;
-    float *obase = a.out + (long long)bv * H * W * CP + grp * 4;
+    using OutT = std::conditional_t<JPL == 4, float, _Float16>;
+    OutT *obase = reinterpret_cast<OutT *>(a.out) + (long long)bv * H * W * CP + grp * JPL;
     for (int t = 0; t < a.tiles_x; ++t) {
         const int tx0 = t * kTileW, set = t % 3;
-        // the listed records that meet this tile, per channel group (at most 4 P each: fits kept[][][])
+        // the listed records that meet this tile, per channel group (at most JPL P each: fits kept[][][])
         for (int i = tid; i < nband; i += kRenderThreads) {
             const int r = band[i];
             if (recs[r].x0 < tx0 + kTileW && recs[r].x1 > tx0) {
                 const int j = recs[r].j;
-                kept[set][j >> 2][atomicAdd(&kept_n[set][j >> 2], 1)] = (unsigned short)(r * 4 + (j & 3));
+                kept[set][j >> SH][atomicAdd(&kept_n[set][j >> SH], 1)] = (unsigned short)(r * JPL + (j & (JPL - 1)));
             }
         }
         if (tid < QP) kept_n[(t + 1) % 3][tid] = 0;  // (its readers finished before the previous barrier)
@@ -183,31 +208,51 @@ __global__ __launch_bounds__(kRenderThreads) void render_keypoints_kernel(const 
         for (int pass = 0; pass < PASSES; ++pass) {
             const int pp = pass * PPP + pix;
             const int x = tx0 + pp % kTileW, y = ty0 + pp / kTileW;
-            float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            RenderAcc<JPL> va;
+            float4 &acc = va.lo;
+            acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if constexpr (JPL == 8) va.hi = acc;
             for (int i = 0; i < nk; ++i) {
                 const int id = kept[set][grp][i];
-                const RenderRec rec = recs[id >> 2];
+                const RenderRec rec = recs[id >> SH];
                 if (x >= rec.x0 && x < rec.x1 && y >= rec.y0 && y < rec.y1) {
                     const float dx = (float)(x - rec.cx), dy = (float)(y - rec.cy);
                     const float g = expf(-((dx * dx + dy * dy) * rec.inv));
-                    const int k = id & 3;
+                    const int k = id & (JPL - 1);
                     acc.x = k == 0 ? fmaxf(acc.x, g) : acc.x;
                     acc.y = k == 1 ? fmaxf(acc.y, g) : acc.y;
                     acc.z = k == 2 ? fmaxf(acc.z, g) : acc.z;
                     acc.w = k == 3 ? fmaxf(acc.w, g) : acc.w;
+                    if constexpr (JPL == 8) {
+                        va.hi.x = k == 4 ? fmaxf(va.hi.x, g) : va.hi.x;
+                        va.hi.y = k == 5 ? fmaxf(va.hi.y, g) : va.hi.y;
+                        va.hi.z = k == 6 ? fmaxf(va.hi.z, g) : va.hi.z;
+                        va.hi.w = k == 7 ? fmaxf(va.hi.w, g) : va.hi.w;
+                    }
                 }
             }
-            if (x < W && y < H) *reinterpret_cast<float4 *>(obase + (y * W + x) * CP) = acc;
+            if (x < W && y < H) {
+                OutT *o = obase + (y * W + x) * CP;
+                if constexpr (JPL == 4) {
+                    *reinterpret_cast<float4 *>(o) = acc;
+                } else {  // one rounding per channel, to nearest even (a plain conversion, as Tensor.half())
+                    const f16x8 h = {(_Float16)acc.x,   (_Float16)acc.y,   (_Float16)acc.z,   (_Float16)acc.w,
+                                     (_Float16)va.hi.x, (_Float16)va.hi.y, (_Float16)va.hi.z, (_Float16)va.hi.w};
+                    *reinterpret_cast<f16x8 *>(o) = h;
+                }
+            }
         }
     }
 }
 
 }  // namespace fvp
 
-extern "C" int fvp_render_keypoints(const void *joints, int joints_f64, const int *count, const unsigned char *vis,
-                                    int B, int V, int P, int J, int H, int W, double image_w, double image_h,
-                                    double sigma, int Cp, float *out_cl, void *stream) {
-    using namespace fvp;
+namespace fvp {
+
+// Host checks and the launch shared by the fp32 (half = false) and fp16 entry points.
+static int render_launch(const void *joints, int joints_f64, const int *count, const unsigned char *vis, int B, int V,
+                         int P, int J, int H, int W, double image_w, double image_h, double sigma, int Cp, void *out_cl,
+                         bool half, void *stream) {
     if (!joints || !count || !out_cl) return FVP_ERR_NULL;
     if (B <= 0 || V <= 0 || P <= 0 || J <= 0 || H <= 0 || W <= 0) return FVP_ERR_SHAPE;
     if (J > kMaxRenderJ || P > kMaxRenderP || Cp < J || Cp % 16 || Cp > 32) return FVP_ERR_SHAPE;
@@ -215,6 +260,7 @@ extern "C" int fvp_render_keypoints(const void *joints, int joints_f64, const in
     if (!(image_w > 0.0) || !(image_h > 0.0) || !(sigma > 0.0) || !isfinite(image_w) || !isfinite(image_h) ||
         !isfinite(sigma))
         return FVP_ERR_SHAPE;
+    if (half && (reinterpret_cast<uintptr_t>(out_cl) & 15)) return FVP_ERR_SHAPE;  // 16-B stores
     RenderArgs a;
     a.joints = joints;
     a.count = count;
@@ -234,11 +280,31 @@ extern "C" int fvp_render_keypoints(const void *joints, int joints_f64, const in
     if (blocks > 0x7fffffffLL) return FVP_ERR_SHAPE;
     const size_t lds = (size_t)P * J * (sizeof(double2) + sizeof(RenderRec) + sizeof(unsigned short)) +
                        (size_t)P * sizeof(RenderPerson);
-    if (Cp == 16)
-        hipLaunchKernelGGL(render_keypoints_kernel<16>, dim3((unsigned)blocks), dim3(kRenderThreads), lds,
-                           (hipStream_t)stream, a);
+    const dim3 grid((unsigned)blocks), block(kRenderThreads);
+    if (Cp == 16 && !half)
+        hipLaunchKernelGGL((render_keypoints_kernel<16, 4>), grid, block, lds, (hipStream_t)stream, a);
+    else if (!half)
+        hipLaunchKernelGGL((render_keypoints_kernel<32, 4>), grid, block, lds, (hipStream_t)stream, a);
+    else if (Cp == 16)
+        hipLaunchKernelGGL((render_keypoints_kernel<16, 8>), grid, block, lds, (hipStream_t)stream, a);
     else
-        hipLaunchKernelGGL(render_keypoints_kernel<32>, dim3((unsigned)blocks), dim3(kRenderThreads), lds,
-                           (hipStream_t)stream, a);
+        hipLaunchKernelGGL((render_keypoints_kernel<32, 8>), grid, block, lds, (hipStream_t)stream, a);
     return (int)hipGetLastError();
+}
+
+}  // namespace fvp
+
+extern "C" int fvp_render_keypoints(const void *joints, int joints_f64, const int *count, const unsigned char *vis,
+                                    int B, int V, int P, int J, int H, int W, double image_w, double image_h,
+                                    double sigma, int Cp, float *out_cl, void *stream) {
+    return fvp::render_launch(joints, joints_f64, count, vis, B, V, P, J, H, W, image_w, image_h, sigma, Cp, out_cl,
+                              false, stream);
+}
+
+extern "C" int fvp_render_keypoints_f16(const void *joints, int joints_f64, const int *count,
+                                        const unsigned char *vis, int B, int V, int P, int J, int H, int W,
+                                        double image_w, double image_h, double sigma, int Cp, void *out_cl_f16,
+                                        void *stream) {
+    return fvp::render_launch(joints, joints_f64, count, vis, B, V, P, J, H, W, image_w, image_h, sigma, Cp,
+                              out_cl_f16, true, stream);
 }

@@ -21,7 +21,10 @@ BasicBlock stages, the deconvolution head, the final conv) into
 The output stays NHWC: ``[N, h, w, Cp]`` with the J joints in channels 0..J-1
 and zeros after them, i.e. exactly the channels-last heatmap layout the
 voxelize gather reads (``fvp_voxelize_cl``), so the views path needs no
-transpose pass (:meth:`FvpPoseResNet.heatmaps_cl`).  ``__call__`` returns the
+transpose pass (:meth:`FvpPoseResNet.heatmaps_cl`).  With
+``heatmaps_cl(views, dtype=torch.float16)`` a 1x1 final layer writes the fp16
+channels-last layout of the fp16 gathers itself (``fvp_conv1x1_cl_f16``), so
+that route needs no cast pass either.  ``__call__`` returns the
 reference's NCHW heatmaps.  Eval mode only (BatchNorm with running statistics).
 """
 from __future__ import annotations
@@ -120,6 +123,7 @@ class FvpPoseResNet:
             self.deconvs.append(ConvLayer(conv, bn, dtype, algo=algo))
             i += 3
         self.final = ConvLayer(module.final_layer, None, dtype, algo=algo)
+        self.last_head_route = None  # the route of the last heatmaps_cl(dtype=torch.float16) (head_route)
         self.num_joints = module.final_layer.out_channels
         # bf16: activations between the layers stay bf16 in HBM (half the bytes,
         # no per-chunk conversion), the stem's output and its max pool included;
@@ -137,6 +141,12 @@ class FvpPoseResNet:
     def forward_nhwc(self, images: torch.Tensor, out: torch.Tensor | None = None) -> Act:
         """images [N,3,H,W] -> NHWC heatmaps Act [N,h,w,Cp] (J channels, zeros after).
         out: optional [N,h,w,Cp] destination of the final layer."""
+        return self.final(self.features_nhwc(images), relu=False, out=out)
+
+    @torch.no_grad()
+    def features_nhwc(self, images: torch.Tensor) -> Act:
+        """images [N,3,H,W] -> the NHWC activations the final layer reads (the deconvolution
+        head's output, resnet.py:198)."""
         if images.device.type != "cuda":
             raise _lib.FvpError(f"fvp: images must be on a HIP device, got {images.device}")
         if self.stem7 is not None:
@@ -150,7 +160,7 @@ class FvpPoseResNet:
             x = b(x)
         for d in self.deconvs:
             x = d(x, relu=True)
-        return self.final(x, relu=False, out=out)
+        return x
 
     def _stem7(self, images: torch.Tensor) -> Act:
         x = images.float().contiguous()
@@ -172,14 +182,39 @@ class FvpPoseResNet:
         """ResNet.forward (resnet.py:187-201): [N,3,H,W] -> [N,J,h,w] fp32."""
         return to_nchw(self.forward_nhwc(images))
 
+    def head_route(self, x: Act | None = None) -> str:
+        """How heatmaps_cl(dtype=torch.float16) gets its fp16 heatmaps from the features `x`
+        (None: fp32 features of the final layer's pitch): "conv1x1_cl_f16" -- the final layer
+        itself writes them (fvp_conv1x1_cl_f16: a 1x1, stride-1, unpadded layer on fp32
+        activations of 16..512 channels, J <= 32) -- or "cast": the fp32 final layer, then
+        ChannelsLastHeatmaps.half() (a 3x3 final layer, the bf16 backbone, J > 32)."""
+        f = self.final
+        ok = (not f.bf16 and f.mode == 0 and (f.KH, f.KW) == (1, 1) and f.stride == (1, 1) and f.pad == (0, 0)
+              and f.Cpi % 16 == 0 and 16 <= f.Cpi <= 512 and f.Cout <= 32
+              and (x is None or (x.t.dtype == torch.float32 and x.t.is_contiguous() and x.Cp == f.Cpi)))
+        return "conv1x1_cl_f16" if ok else "cast"
+
     @torch.no_grad()
-    def heatmaps_cl(self, views: torch.Tensor) -> ChannelsLastHeatmaps:
+    def heatmaps_cl(self, views: torch.Tensor, dtype: torch.dtype | None = None) -> ChannelsLastHeatmaps:
         """All views of a batch in one pass: views [B,V,3,H,W] -> channels-last
         heatmaps [B,V,h,w,Cp] (the stack of faster_voxelpose.py:75 without the
-        per-view loop, the stack copy, or a transpose before the voxelize)."""
+        per-view loop, the stack copy, or a transpose before the voxelize).
+        dtype=torch.float16: the fp16 layout of the fp16 gathers, by the route
+        head_route names (``last_head_route`` afterwards)."""
+        if dtype not in (None, torch.float32, torch.float16):
+            raise _lib.FvpError(f"fvp: heatmaps_cl: dtype must be None, torch.float32 or torch.float16, got {dtype}")
         B, V = views.shape[:2]
-        act = self.forward_nhwc(views.reshape((B * V,) + tuple(views.shape[2:])))
-        return ChannelsLastHeatmaps(act.t.view(B, V, act.H, act.W, act.Cp), self.num_joints)
+        images = views.reshape((B * V,) + tuple(views.shape[2:]))
+        if dtype != torch.float16:
+            act = self.forward_nhwc(images)
+            return ChannelsLastHeatmaps(act.t.view(B, V, act.H, act.W, act.Cp), self.num_joints)
+        x = self.features_nhwc(images)
+        self.last_head_route = self.head_route(x)
+        if self.last_head_route == "cast":
+            act = self.final(x, relu=False)
+            return ChannelsLastHeatmaps(act.t.view(B, V, act.H, act.W, act.Cp), self.num_joints).half()
+        out = conv1x1_cl_f16(self.final, x)
+        return ChannelsLastHeatmaps(out.view(B, V, x.H, x.W, out.shape[3]), self.num_joints)
 
     def flops(self, N: int, H: int, W: int) -> int:
         """Multiply-add FLOPs of one forward on N images of H x W (MFMA work, padding excluded)."""
@@ -201,6 +236,17 @@ class FvpPoseResNet:
             total += d.flops(dummy(d.Cpi, h, w))
             h, w = d.out_hw(h, w)
         return total
+
+
+def conv1x1_cl_f16(layer: ConvLayer, x: Act) -> torch.Tensor:
+    """A 1x1 fp32 ConvLayer of <= 32 output channels (its folded scale / shift, no ReLU) on
+    fp32 activations, written as fp16 channels-last rows [N,H,W,Cpo] in one launch
+    (fvp_conv1x1_cl_f16): the eligible case of FvpPoseResNet.head_route."""
+    out = torch.empty((x.N, x.H, x.W, layer.Cpo), dtype=torch.float16, device=x.t.device)
+    if out.numel():
+        _lib.call("fvp_conv1x1_cl_f16", _ptr(x.t), x.N * x.H * x.W, x.Cp, _ptr(layer.wpack), layer.Cpo_w, layer.Cout,
+                  _ptr(layer.scale), _ptr(layer.shift), layer.Cpo, _ptr(out), _stream(out))
+    return out
 
 
 def cached(module: nn.Module, dtype=torch.float32, algo: int | None = None) -> FvpPoseResNet:

@@ -150,7 +150,7 @@ def to_channels_last(planar: torch.Tensor, dtype: torch.dtype | None = None) -> 
     return ChannelsLastHeatmaps(t, J)
 
 
-def share_channels_last(heatmaps) -> ChannelsLastHeatmaps | None:
+def share_channels_last(heatmaps, dtype: torch.dtype | None = None) -> ChannelsLastHeatmaps | None:
     """Lay `heatmaps` out channels-last once and attach the copy (the fused
     HDN forward does this so that the JLN, handed the same tensor object,
     reads the same copy, then drops it: release_shared): planar fp32 tensors of
@@ -158,7 +158,13 @@ def share_channels_last(heatmaps) -> ChannelsLastHeatmaps | None:
     as it is; one left by an earlier call of this function is NOT -- the caller
     may have refilled the same buffer through ``.data``, DLPack or the C ABI,
     which do not move ``_version`` -- so every fused forward lays out anew.
+    dtype=torch.float16 (FvpOptions.heatmaps_dtype): the one layout pass writes
+    the fp16 copy (to_channels_last(dtype=torch.float16), half the bytes) and
+    the gathers take their fp16 route; a copy already attached keeps its dtype.
     Returns the copy in use, if any."""
+    if dtype not in (None, torch.float32, torch.float16):
+        raise _lib.FvpError(f"fvp: share_channels_last: dtype must be None, torch.float32 or torch.float16, "
+                            f"got {dtype}")
     cl = channels_last_of(heatmaps, reuse_shared=False)
     if cl is not None or not isinstance(heatmaps, torch.Tensor):
         return cl
@@ -167,7 +173,7 @@ def share_channels_last(heatmaps) -> ChannelsLastHeatmaps | None:
             or heatmaps.shape[2] > 32 or heatmaps.shape[0] == 0
             or (torch.is_grad_enabled() and heatmaps.requires_grad)):
         return None
-    cl = to_channels_last(heatmaps)
+    cl = to_channels_last(heatmaps, dtype=torch.float16 if dtype == torch.float16 else None)
     attach(heatmaps, cl, shared=True)
     return cl
 
@@ -205,7 +211,7 @@ def pack_keypoints(all_preds, max_people: int | None = None):
 
 
 def render_keypoints(joints: torch.Tensor, count: torch.Tensor, vis: torch.Tensor | None = None, *, image_size,
-                     heatmap_size, sigma: float) -> ChannelsLastHeatmaps:
+                     heatmap_size, sigma: float, dtype: torch.dtype | None = None) -> ChannelsLastHeatmaps:
     """Input heatmaps painted from 2-D keypoints on the device, channels-last,
     in one launch (fvp_render_keypoints): JointsDataset.generate_input_heatmap
     (lib/dataset/JointsDataset.py:368-447) with ``data_augmentation = False``,
@@ -219,6 +225,9 @@ def render_keypoints(joints: torch.Tensor, count: torch.Tensor, vis: torch.Tenso
     count   [B, V] int32: people of each view (rows at or beyond it are never read)
     vis     [B, V, P, J] uint8 or bool, optional: 0 = joint not painted
     image_size, heatmap_size  (W, H) as NETWORK.IMAGE_SIZE / HEATMAP_SIZE;  sigma: NETWORK.SIGMA
+    dtype   None / torch.float32, or torch.float16: the fp16 channels-last layout the
+            fp16 gathers read, written by the same launch (fvp_render_keypoints_f16) --
+            bit for bit ``render_keypoints(...).half()`` without the cast pass
 
     A person with a non-finite coordinate is skipped (the reference raises).
     Out of scope: the ``'gt'`` source (3-D joints projected through the cameras
@@ -226,6 +235,8 @@ def render_keypoints(joints: torch.Tensor, count: torch.Tensor, vis: torch.Tenso
     training-time random augmentation."""
     from . import ops
 
+    if dtype not in (None, torch.float32, torch.float16):
+        raise _lib.FvpError(f"fvp: render_keypoints: dtype must be None, torch.float32 or torch.float16, got {dtype}")
     if not isinstance(joints, torch.Tensor) or joints.dim() != 5 or joints.shape[4] != 2 \
             or joints.dtype not in (torch.float32, torch.float64):
         raise _lib.FvpError(f"fvp: render_keypoints takes joints fp64 / fp32 [B,V,P,J,2], got "
@@ -254,5 +265,6 @@ def render_keypoints(joints: torch.Tensor, count: torch.Tensor, vis: torch.Tenso
     if int(W) != W or int(H) != H or W < 1 or H < 1 or not (img_w > 0 and img_h > 0 and sigma > 0):
         raise _lib.FvpError(f"fvp: render_keypoints: image {image_size}, heatmap {heatmap_size}, sigma {sigma}")
     ops.forward_only(joints)
-    t = ops.render_keypoints(joints, count, vis, float(img_w), float(img_h), int(H), int(W), float(sigma))
+    op = ops.render_keypoints_f16 if dtype == torch.float16 else ops.render_keypoints
+    t = op(joints, count, vis, float(img_w), float(img_h), int(H), int(W), float(sigma))
     return ChannelsLastHeatmaps(t, J)

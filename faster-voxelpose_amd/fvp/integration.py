@@ -41,6 +41,7 @@ import sys
 
 import torch
 
+from . import _lib
 from . import backbone as fvp_backbone
 from . import cnn as fvp_cnn
 from . import heatmaps as fvp_heatmaps
@@ -79,7 +80,19 @@ class FvpOptions:
       ONCE for the batch (fvp.heatmaps.to_channels_last) and attaches the copy
       to the heatmaps tensor, so its own gather and the JLN's person planes
       (the same tensor object, faster_voxelpose.py:85-93) both read it in
-      place -- one layout pass per batch instead of one per consumer."""
+      place -- one layout pass per batch instead of one per consumer.
+    heatmaps_dtype: torch.float16 = the heatmaps reach the gathers as fp16
+      channels-last, written at their source: fused_fvp_forward's backbone writes
+      them from its last layer (FvpPoseResNet.heatmaps_cl(dtype=torch.float16)),
+      fused_hdn_forward's one layout pass of planar fp32 heatmaps writes fp16
+      (share_channels_last(dtype=torch.float16)), and fvp.heatmaps.render_keypoints
+      takes the same dtype for the 'pred' path.  Everything after the heatmaps is
+      the reference arithmetic in fp32 on the fp16-rounded values (opt-in
+      precision; the default fp32 stays bit-identical).  Limit: the on-the-fly
+      person path has no fp16 channels-last kernel and raises, so the option
+      serves rigs whose JLN fine grid is cached -- up to 16 cameras at the
+      reference's 253 x 253 x 64 fine grid (fvp.project_individual.PERSON_OTF_GRID_BYTES:
+      17 cameras and more go on the fly)."""
     cnn: bool = False
     cnn_dtype: torch.dtype = torch.float32
     backbone: bool = False
@@ -88,9 +101,16 @@ class FvpOptions:
     recompute_cube_bytes: int = 512 << 20
     c2c_graphs: bool = True
     share_layout: bool = True
+    heatmaps_dtype: torch.dtype = torch.float32
 
 
 DEFAULT_OPTIONS = FvpOptions()
+
+
+def _heatmaps_dtype(dtype) -> torch.dtype:
+    if dtype not in (None, torch.float32, torch.float16):
+        raise _lib.FvpError(f"fvp: heatmaps_dtype must be torch.float32 or torch.float16, got {dtype}")
+    return torch.float32 if dtype is None else dtype
 
 
 def options_of(module) -> FvpOptions:
@@ -103,13 +123,16 @@ def set_options(model, **changes) -> FvpOptions:
     """Give `model` and every submodule (an nn.Module's modules(); or just the
     object) its own options: the current ones with `changes` applied.  No
     parameters or buffers are added, so state_dict is unchanged."""
+    if "heatmaps_dtype" in changes:
+        changes["heatmaps_dtype"] = _heatmaps_dtype(changes["heatmaps_dtype"])
     opts = dataclasses.replace(options_of(model), **changes)
     for m in (model.modules() if hasattr(model, "modules") else [model]):
         object.__setattr__(m, "fvp_options", opts)  # plain attribute (not a submodule / parameter)
     return opts
 
 
-def install(fused: bool = True, modules=None, cnn: bool = False, backbone: bool = False) -> dict:
+def install(fused: bool = True, modules=None, cnn: bool = False, backbone: bool = False,
+            heatmaps_dtype: torch.dtype | None = None) -> dict:
     """Patch the already-importable reference modules.  Returns what was patched.
 
     cnn=True (with fused=True): in eval mode the fused forwards run CenterNet,
@@ -117,10 +140,13 @@ def install(fused: bool = True, modules=None, cnn: bool = False, backbone: bool 
     torch's, in fp32, and WeightNet as one fused launch; cnn="bf16": bf16
     operands with fp32 accumulation for the MFMA convolutions (opt-in, ~1e-2
     relative).  backbone=True / "bf16": the same for the PoseResNet backbone.
+    heatmaps_dtype=torch.float16: fp16 channels-last heatmaps written at their
+    source (FvpOptions.heatmaps_dtype, with its limit); None = fp32.
     These become the FvpOptions of the patched classes (per-model overrides:
     set_options)."""
     opts = FvpOptions(cnn=bool(cnn), cnn_dtype=torch.bfloat16 if cnn == "bf16" else torch.float32,
-                      backbone=bool(backbone), backbone_dtype=torch.bfloat16 if backbone == "bf16" else torch.float32)
+                      backbone=bool(backbone), backbone_dtype=torch.bfloat16 if backbone == "bf16" else torch.float32,
+                      heatmaps_dtype=_heatmaps_dtype(heatmaps_dtype))
     mods = modules if modules is not None else sys.modules
     patched = {}
 
@@ -194,7 +220,7 @@ def fused_hdn_forward(self, heatmaps, meta, cameras, resize_transform):
     opts = options_of(self)
     pl_ = self.project_layer
     if opts.share_layout:
-        fvp_heatmaps.share_channels_last(heatmaps)
+        fvp_heatmaps.share_channels_last(heatmaps, dtype=opts.heatmaps_dtype)
     recompute = opts.recompute_columns
     if recompute is None:
         X, Y, Z = (int(v) for v in pl_.voxels_per_axis)
@@ -244,13 +270,14 @@ def fused_fvp_forward(self, backbone=None, views=None, meta=None, targets=None, 
                       resize_transform=None):
     """FasterVoxelPoseNet.forward (faster_voxelpose.py:51-162) with the views
     path on the fvp backbone in eval mode: all B*V views in one pass, heatmaps
-    written channels-last once and handed to the HDN / JLN gathers in place
-    (fvp.heatmaps.attach); everything after it is the reference's forward."""
+    written channels-last once (fp32, or fp16 with FvpOptions.heatmaps_dtype)
+    and handed to the HDN / JLN gathers in place (fvp.heatmaps.attach);
+    everything after it is the reference's forward."""
     opts = options_of(self)
     attached = None
     if (views is not None and backbone is not None and not self.training and hasattr(backbone, "deconv_layers")
             and _fvp_backbone_ok(backbone, views, opts)):
-        cl = fvp_backbone.cached(backbone, opts.backbone_dtype).heatmaps_cl(views)
+        cl = fvp_backbone.cached(backbone, opts.backbone_dtype).heatmaps_cl(views, dtype=opts.heatmaps_dtype)
         input_heatmaps, views = cl.planar(), None  # [B,V,J,H,W], carrying the channels-last copy
         attached = input_heatmaps
     try:

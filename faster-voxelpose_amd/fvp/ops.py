@@ -748,13 +748,15 @@ def render_cp(J: int) -> int:
 
 def render_keypoints_into(joints: torch.Tensor, count: torch.Tensor, vis: Optional[torch.Tensor], image_w: float,
                           image_h: float, sigma: float, out: torch.Tensor) -> torch.Tensor:
-    """fvp_render_keypoints into `out` [B,V,H,W,Cp] fp32 (every element is overwritten).  Operands as
-    fvp.heatmaps.render_keypoints validates them: contiguous, on out's device."""
+    """fvp_render_keypoints into `out` [B,V,H,W,Cp] fp32, or fvp_render_keypoints_f16 into an fp16
+    `out` (every element is overwritten).  Operands as fvp.heatmaps.render_keypoints validates
+    them: contiguous, on out's device."""
     B, V, P, J, _ = joints.shape
     H, W, cp = out.shape[2], out.shape[3], out.shape[4]
     if (joints.dtype not in (torch.float32, torch.float64) or not joints.is_contiguous() or joints.shape[4] != 2
             or count.dtype != torch.int32 or not count.is_contiguous() or tuple(count.shape) != (B, V)
-            or out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape[:2]) != (B, V)
+            or out.dtype not in (torch.float32, torch.float16) or not out.is_contiguous()
+            or tuple(out.shape[:2]) != (B, V)
             or (vis is not None and (vis.dtype != torch.uint8 or not vis.is_contiguous()
                                      or tuple(vis.shape) != (B, V, P, J)))):
         raise _lib.FvpError(f"fvp: render_keypoints operands: joints {tuple(joints.shape)} {joints.dtype}, count "
@@ -763,8 +765,9 @@ def render_keypoints_into(joints: torch.Tensor, count: torch.Tensor, vis: Option
         if t is not None and (t.device.type != "cuda" or t.device != out.device):
             raise _lib.FvpError(f"fvp: render_keypoints operands must share one HIP device, got {t.device}")
     if out.numel():
-        _lib.call("fvp_render_keypoints", _ptr(joints), int(joints.dtype == torch.float64), _ptr(count), _ptr(vis),
-                  B, V, P, J, H, W, float(image_w), float(image_h), float(sigma), cp, _ptr(out), _stream(out))
+        _lib.call(_f16("fvp_render_keypoints", out), _ptr(joints), int(joints.dtype == torch.float64), _ptr(count),
+                  _ptr(vis), B, V, P, J, H, W, float(image_w), float(image_h), float(sigma), cp, _ptr(out),
+                  _stream(out))
     return out
 
 
@@ -784,6 +787,24 @@ def render_keypoints(joints: torch.Tensor, count: torch.Tensor, vis: Optional[to
 def _(joints, count, vis, image_w, image_h, H, W, sigma):
     B, V, _, J, _ = joints.shape
     return joints.new_empty((B, V, H, W, render_cp(J)), dtype=torch.float32)
+
+
+@_custom_op("fvp::render_keypoints_f16", mutates_args=(), device_types="cuda")
+def render_keypoints_f16(joints: torch.Tensor, count: torch.Tensor, vis: Optional[torch.Tensor], image_w: float,
+                         image_h: float, H: int, W: int, sigma: float) -> torch.Tensor:
+    """render_keypoints writing fp16 channels-last heatmaps [B,V,H,W,16*ceil(J/16)] directly
+    (fvp_render_keypoints_f16, one launch): bit for bit render_keypoints(...).half()."""
+    if joints.dim() != 5:
+        raise _lib.FvpError(f"fvp: render_keypoints joints must be [B,V,P,J,2], got {tuple(joints.shape)}")
+    B, V, _, J, _ = joints.shape
+    out = torch.empty((B, V, H, W, render_cp(J)), dtype=torch.float16, device=joints.device)
+    return render_keypoints_into(joints, count, vis, image_w, image_h, sigma, out)
+
+
+@render_keypoints_f16.register_fake
+def _(joints, count, vis, image_w, image_h, H, W, sigma):
+    B, V, _, J, _ = joints.shape
+    return joints.new_empty((B, V, H, W, render_cp(J)), dtype=torch.float16)
 
 
 def mask_nonzero(mask: torch.Tensor) -> torch.Tensor:

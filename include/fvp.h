@@ -644,6 +644,34 @@ int fvp_nchw_to_nhwc_f16(const void *in, int in_half, int N, int C, int H, int W
 int fvp_render_keypoints(const void *joints, int joints_f64, const int *count, const unsigned char *vis, int B,
                          int V, int P, int J, int H, int W, double image_w, double image_h, double sigma, int Cp,
                          float *out_cl, void *stream);
+/* The same painter (JointsDataset.py:368-447, :265-279) writing the fp16
+ * channels-last layout fvp_voxelize_cl_f16 / fvp_person_planes_cl_f16 read in
+ * place, so the 'pred' path needs no cast pass.  Same arguments and host checks;
+ *   out_cl_f16  device [B][V][H][W][Cp] fp16, Cp in {16, 32}, Cp >= J, 16-B aligned
+ * Each channel's fp32 maximum is rounded once, to nearest even: the result equals
+ * fvp_render_keypoints followed by Tensor.half() bit for bit.  Every element is
+ * written once, padding channels as +0. */
+int fvp_render_keypoints_f16(const void *joints, int joints_f64, const int *count, const unsigned char *vis, int B,
+                             int V, int P, int J, int H, int W, double image_w, double image_h, double sigma, int Cp,
+                             void *out_cl_f16, void *stream);
+
+/* PoseResNet's final_layer (lib/models/resnet.py:122-128 with FINAL_CONV_KERNEL: 1,
+ * applied at :199: a 1x1 convolution Cin -> J plus bias) writing fp16
+ * channels-last heatmap rows directly -- the input of fvp_voxelize_cl_f16 --
+ * instead of fp32 rows and a cast pass:
+ *   out[p][co] = half(scale[co] * sum_ci in[p][ci] * w[ci * ldw + co] + shift[co])   co < Cout
+ *              = +0                                                          Cout <= co < Cp
+ * with fp32 accumulation on the matrix cores and one rounding to nearest even
+ * (+-inf beyond 65504, as Tensor.half()).
+ *   in     device [npix][Cpi] fp32, 16-B aligned, Cpi % 16 == 0, 16 <= Cpi <= 512
+ *   w      device [Cpi][ldw] fp32 (the wpack of a 1x1 fvp_conv2d_nhwc_ex layer: rows
+ *          past Cin zero); only columns < Cout are read, ldw >= Cout
+ *   scale, shift  device fp32; only elements < Cout are read
+ *   out_f16 device [npix][Cp] fp16, Cp in {16, 32}, Cout <= Cp, 16-B aligned
+ * A pixel's result depends on its row and the weights only (no split-K, no
+ * launch-size-dependent order).  Anything else: FVP_ERR_SHAPE. */
+int fvp_conv1x1_cl_f16(const float *in, long long npix, int Cpi, const float *w, int ldw, int Cout,
+                       const float *scale, const float *shift, int Cp, void *out_f16, void *stream);
 
 /* Roofline calibration (not on the product path): a float4 streaming copy of
  * `bytes` (multiple of 16) from src to dst; bench.py reports the op's HBM
