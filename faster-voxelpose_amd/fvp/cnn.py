@@ -735,20 +735,28 @@ class Net1D:
             out, Cf, Lf = n.conv(module.output_hm, None, x, C, L, relu=False)
         except (ValueError, AttributeError, IndexError):
             return None
-        shapes = [(o[2], 2 * o[4] if o[0] == 1 else o[4]) for o in n.ops if o[0] != 2]  # (cout, Lout)
+        return n._finish(cin0, L0, out, Cf, Lf, module.output_hm.weight.device)
+
+    def _finish(self, cin0: int, L0: int, out: int, Cf: int, Lf: int, dev, lg: int | None = None):
+        """The launch plan of the ops appended so far, whose result is buffer `out`
+        ([Cf][Lf]): self with the program and parameter tensors on `dev`; None if no
+        positions-per-item count (`lg`, when given: that one) covers every conv with the
+        block's threads, False if the LDS total exceeds the CU's 160 KB."""
+        shapes = [(o[2], 2 * o[4] if o[0] == 1 else o[4]) for o in self.ops if o[0] != 2]  # (cout, Lout)
         # positions per thread item: 4 (4 FMAs per LDS weight read), 8 where cout x ceil(L / 4)
         # exceeds the kernel's 4 items x 256 threads
-        lg = next((g for g in (4, 8) if all(c * -(-Lo // g) <= 1024 for c, Lo in shapes)), None)
+        fits = [g for g in (4, 8) if all(c * -(-Lo // g) <= 1024 for c, Lo in shapes)]
         if lg is None:
+            lg = fits[0] if fits else None
+        if lg not in fits:
             return None
-        lds = _lib.load().fvp_conv1d_net_lds_bytes(n.slot, n.nbuf, n.wchunk, lg)
+        lds = _lib.load().fvp_conv1d_net_lds_bytes(self.slot, self.nbuf, self.wchunk, lg)
         if lds > 160 * 1024:
             return False
-        dev = module.output_hm.weight.device
-        n.prog = torch.tensor(n.ops, dtype=torch.int32, device=dev).contiguous()
-        n.param = torch.cat(n.params).contiguous().to(dev)
-        n.cin0, n.L0, n.out_buf, n.cout, n.Lout, n.lg = cin0, L0, out, Cf, Lf, lg
-        return n
+        self.prog = torch.tensor(self.ops, dtype=torch.int32, device=dev).contiguous()
+        self.param = torch.cat(self.params).contiguous().to(dev)
+        self.cin0, self.L0, self.out_buf, self.cout, self.Lout, self.lg = cin0, L0, out, Cf, Lf, lg
+        return self
 
     def __call__(self, x: torch.Tensor) -> torch.Tensor:
         x = x.float().contiguous()
