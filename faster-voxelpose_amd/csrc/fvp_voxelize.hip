@@ -35,6 +35,7 @@
 // tap and the camera sum order are the reference's (fvp_device.h: torch's
 // CPU mean over the views folds complete blocks of 16 cameras, CASC = V > 16),
 // so the result is bit-exact.
+#include <algorithm>
 #include <type_traits>
 
 #include "fvp_layout.h"
@@ -56,6 +57,12 @@ struct CoordSource {
     int x_off;              // (OTF) first x-row of an x-slab launch (0: the whole grid)
 };
 
+// Whether a block of T voxels takes the vector epilogue (store_stage; the host
+// reports the same predicate per launch through fvp_voxelize_plan).
+__host__ __device__ __forceinline__ bool stage_vec(int T, int SP, int Z, long long N, bool cube16) {
+    return ((T | SP | Z | (int)(N & 3)) & 3) == 0 && cube16;
+}
+
 // Epilogue of a gather block: the stage [NF][JP][SP] (clamped means, column-
 // major within the block's columns) -> the cube runs and the xy max over z.
 template <int NF, int JP>
@@ -68,7 +75,7 @@ __device__ __forceinline__ void store_stage(const float *__restrict__ stage, int
     // the z-max reads 4 voxels per LDS load: a sixth of the store instructions
     // and independent LDS reads instead of a 20-long dependent chain
     // (tools/gather_probe.py FULL2: C2 8 frames 62.1 -> 59.8 us).
-    const bool vec = ((T | SP | Z | (int)(N & 3)) & 3) == 0 && cube16;
+    const bool vec = stage_vec(T, SP, Z, N, cube16);
 #pragma unroll
     for (int f = 0; f < NF; ++f) {
         const float *fst = stage + f * JP * SP;
@@ -519,10 +526,50 @@ static int gather_cfg(int frames, int NF, int V, int X, int Y, int Z, GatherCfg 
     return c.lds > 160 * 1024 ? FVP_ERR_SHAPE : FVP_OK;
 }
 
+// Where fvp_voxelize_plan collects a call's gather launches: with a sink in the
+// job every entry point walks its own code -- slices, frame groups, chunks,
+// gather_cfg -- and launch_gather writes a record instead of launching (the
+// layout passes are skipped, no pointer is dereferenced).
+struct PlanSink {
+    long long *rec;  // [cap][FVP_VOXELIZE_PLAN_FIELDS]
+    int cap, n;      // n counts every record, also those beyond cap
+    int j0;          // first joint of the slice being walked
+};
+
+// One gather launch, or its record: status FVP_OK for a launch made,
+// FVP_ERR_SHAPE for the one gather_cfg refused (the call ends there).
+template <int LPV, bool PAIR, bool OTF, bool CASC, int NF, int JPL>
+static void plan_record(PlanSink &p, int f0, int nb, const GatherCfg &c, int J, int X, int Y, int Z, const float *cube,
+                        size_t tab_bytes, int status) {
+    if (p.n < p.cap) {
+        long long *r = p.rec + (size_t)p.n * FVP_VOXELIZE_PLAN_FIELDS;
+        const int VPP = 256 / LPV;
+        const long long XY = (long long)X * Y, N = XY * Z;
+        const int last = (int)(XY - (long long)(c.col_blocks - 1) * c.cols);  // columns of the last block
+        const bool cube16 = ((unsigned long long)cube & 15ull) == 0;
+        r[0] = p.j0;
+        r[1] = JPL == 8 ? (OTF ? 4 : 3) : (OTF ? 2 : 1);
+        r[2] = LPV, r[3] = JPL, r[4] = PAIR, r[5] = CASC, r[6] = NF, r[7] = f0, r[8] = nb;
+        r[9] = c.cols, r[10] = c.band, r[11] = c.col_blocks, r[12] = c.SP, r[13] = (long long)c.lds;
+        r[14] = (c.cols * Z + VPP - 1) / VPP;
+        r[15] = stage_vec(c.cols * Z, c.SP, Z, N, cube16);
+        r[16] = stage_vec(last * Z, c.SP, Z, N, cube16);
+        r[17] = status;
+        r[18] = (long long)(nb / NF) * c.col_blocks;
+        r[19] = last;
+        r[20] = (last * Z + VPP - 1) / VPP;
+        r[21] = (long long)tab_bytes;
+        r[22] = OTF, r[23] = J;
+    }
+    ++p.n;
+}
+
+// tab_bytes: what the launch reads of the workspace (0: heatmaps read in place).
 template <int LPV, bool PAIR, bool OTF, bool CASC, int NF, int JPL = 4>
 static void launch_gather(const void *tab, int f0, int nb, const GatherCfg &c, const CoordSource &src,
                           const int32_t *grid_index, int V, int J, int Jst, int H, int W, int X, int Y, int Z,
-                          float *cube, float *xy, unsigned pixb, hipStream_t s) {
+                          float *cube, float *xy, unsigned pixb, hipStream_t s, PlanSink *plan, size_t tab_bytes) {
+    if (plan) return plan_record<LPV, PAIR, OTF, CASC, NF, JPL>(*plan, f0, nb, c, J, X, Y, Z, cube, tab_bytes, FVP_OK);
     const dim3 grid((unsigned)(nb / NF * c.col_blocks));
     const bool cube16 = ((unsigned long long)cube & 15ull) == 0;  // float4 epilogue stores
     if constexpr (JPL == 8 && OTF)
@@ -551,6 +598,7 @@ struct VoxJob {
     int V, J, Jst, H, W, X, Y, Z;
     const int32_t *grid_index;
     float *cube, *xy;
+    PlanSink *plan;  // fvp_voxelize_plan: record the launches instead of making them
 };
 
 // Frames [first, last) of the batch (a multiple of NF of them), chunk by chunk:
@@ -562,21 +610,30 @@ static int run_chunks(const T *hm, int first, int last, const VoxJob &j, const C
     const int B = last - first;
     const int chunk = max(NF, chunk_frames(B, j.V, j.J, j.H, j.W, half) / NF * NF);
     GatherCfg c;
-    if (gather_cfg<LPV, OTF>(min(chunk, B), NF, j.V, j.X, j.Y, j.Z, c) != FVP_OK) return FVP_ERR_SHAPE;
+    if (gather_cfg<LPV, OTF>(min(chunk, B), NF, j.V, j.X, j.Y, j.Z, c) != FVP_OK) {
+        if (j.plan)
+            plan_record<LPV, PAIR, OTF, CASC, NF, 4>(*j.plan, first, min(chunk, B), c, j.J, j.X, j.Y, j.Z, j.cube, 0,
+                                                     FVP_ERR_SHAPE);
+        return FVP_ERR_SHAPE;
+    }
     const size_t frame_elems = (size_t)j.V * j.Jst * j.H * j.W;
     for (int f0 = first; f0 < last; f0 += chunk) {
         const int nb = min(chunk, last - f0);
         const T *hsrc = hm + (size_t)f0 * frame_elems;
-        if constexpr (PAIR) {  // (J <= 16: never sliced)
+        if (j.plan) {
+            // (no layout pass)
+        } else if constexpr (PAIR) {  // (J <= 16: never sliced)
             launch_pairs<NF>(reinterpret_cast<const _Float16 *>(hsrc), nb, j.V, j.J, j.H, j.W,
                              reinterpret_cast<uint4 *>(ws), s);
         } else {
             launch_layout<LPV, T, NF>(hsrc, nb, j.V, j.J, j.Jst, j.H, j.W, reinterpret_cast<float *>(ws), s);
         }
         launch_gather<LPV, PAIR, OTF, CASC, NF>(ws, f0, nb, c, src, j.grid_index, j.V, j.J, j.Jst, j.H, j.W, j.X, j.Y,
-                                               j.Z, j.cube, j.xy, 4u * 4u * LPV, s);
+                                               j.Z, j.cube, j.xy, 4u * 4u * LPV, s, j.plan,
+                                               (size_t)nb * (PAIR ? pair_frame_bytes(j.V, j.H, j.W)
+                                                                  : cl_frame_bytes(j.V, j.J, j.H, j.W)));
     }
-    return (int)hipGetLastError();
+    return j.plan ? FVP_OK : (int)hipGetLastError();
 }
 
 // Heatmaps already channels-last ([B][V][H][W][cp] fp32, the slice's joints
@@ -588,10 +645,14 @@ static int run_direct(const float *hm_cl, int cp, int B, const VoxJob &j, const 
     auto go = [&](auto lpv) -> int {
         constexpr int LPV = decltype(lpv)::value;
         GatherCfg c;
-        if (gather_cfg<LPV, OTF>(B, 1, j.V, j.X, j.Y, j.Z, c) != FVP_OK) return FVP_ERR_SHAPE;
+        if (gather_cfg<LPV, OTF>(B, 1, j.V, j.X, j.Y, j.Z, c) != FVP_OK) {
+            if (j.plan)
+                plan_record<LPV, false, OTF, CASC, 1, 4>(*j.plan, 0, B, c, j.J, j.X, j.Y, j.Z, j.cube, 0, FVP_ERR_SHAPE);
+            return FVP_ERR_SHAPE;
+        }
         launch_gather<LPV, false, OTF, CASC, 1>(hm_cl, 0, B, c, src, j.grid_index, j.V, j.J, j.Jst, j.H, j.W, j.X,
-                                               j.Y, j.Z, j.cube, j.xy, pixb, s);
-        return (int)hipGetLastError();
+                                               j.Y, j.Z, j.cube, j.xy, pixb, s, j.plan, 0);
+        return j.plan ? FVP_OK : (int)hipGetLastError();
     };
     switch (lanes_per_voxel(j.J)) {
         case 1: return go(std::integral_constant<int, 1>{});
@@ -611,10 +672,14 @@ static int run_direct_h(const _Float16 *hm_cl, int cp, int B, const VoxJob &j, c
     auto go = [&](auto lpv) -> int {
         constexpr int LPV = decltype(lpv)::value;
         GatherCfg c;
-        if (gather_cfg<LPV, OTF, 8>(B, 1, j.V, j.X, j.Y, j.Z, c) != FVP_OK) return FVP_ERR_SHAPE;
+        if (gather_cfg<LPV, OTF, 8>(B, 1, j.V, j.X, j.Y, j.Z, c) != FVP_OK) {
+            if (j.plan)
+                plan_record<LPV, false, OTF, CASC, 1, 8>(*j.plan, 0, B, c, j.J, j.X, j.Y, j.Z, j.cube, 0, FVP_ERR_SHAPE);
+            return FVP_ERR_SHAPE;
+        }
         launch_gather<LPV, false, OTF, CASC, 1, 8>(hm_cl, 0, B, c, src, j.grid_index, j.V, j.J, j.Jst, j.H, j.W, j.X,
-                                                  j.Y, j.Z, j.cube, j.xy, pixb, s);
-        return (int)hipGetLastError();
+                                                  j.Y, j.Z, j.cube, j.xy, pixb, s, j.plan, 0);
+        return j.plan ? FVP_OK : (int)hipGetLastError();
     };
     switch (lanes_per_voxel_h(j.J)) {
         case 1: return go(std::integral_constant<int, 1>{});
@@ -673,7 +738,7 @@ static size_t workspace_bytes(int B, int V, int J, int H, int W, bool half);
 template <bool OTF, typename T>
 static int voxelize_any(const T *hm, int B, int V, int J, int H, int W, const CoordSource &src,
                         const int32_t *grid_index, int X, int Y, int Z, float *cube, float *xy, void *ws,
-                        size_t ws_bytes, hipStream_t s) {
+                        size_t ws_bytes, hipStream_t s, PlanSink *plan = nullptr) {
     const bool half = sizeof(T) == 2;
     const int J1 = slice_joints(J);
     const size_t need = workspace_bytes(B, V, J, H, W, half);
@@ -682,7 +747,8 @@ static int voxelize_any(const T *hm, int B, int V, int J, int H, int W, const Co
     const size_t N = (size_t)X * Y * Z, XY = (size_t)X * Y, HW = (size_t)H * W;
     for (int j0 = 0; j0 < J; j0 += kJointSlice) {
         const VoxJob job{V, min(kJointSlice, J - j0), J, H, W, X, Y, Z, grid_index, cube ? cube + j0 * N : nullptr,
-                         xy ? xy + j0 * XY : nullptr};
+                         xy ? xy + j0 * XY : nullptr, plan};
+        if (plan) plan->j0 = j0;
         const T *h = hm + j0 * HW;
         const int st = V > 16 ? voxelize_lpv<OTF, true, T>(h, B, job, src, ws, s)
                               : voxelize_lpv<OTF, false, T>(h, B, job, src, ws, s);
@@ -694,14 +760,16 @@ static int voxelize_any(const T *hm, int B, int V, int J, int H, int W, const Co
 // Channels-last input: the slice's channels start at hm_cl + j0 (cp >= j0 + 4 * LPV(slice) for every slice).
 template <bool OTF>
 static int voxelize_cl_any(const float *hm_cl, int cp, int B, int V, int J, int H, int W, const CoordSource &src,
-                           const int32_t *grid_index, int X, int Y, int Z, float *cube, float *xy, hipStream_t s) {
+                           const int32_t *grid_index, int X, int Y, int Z, float *cube, float *xy, hipStream_t s,
+                           PlanSink *plan = nullptr) {
     const int jl = ((J - 1) / kJointSlice) * kJointSlice;  // first joint of the last slice
     if (cp % 4 || cp < jl + 4 * lanes_per_voxel(J - jl)) return FVP_ERR_SHAPE;
     if ((size_t)H * W * cp * 4 > 0x7fffffffull) return FVP_ERR_SHAPE;  // 32-bit tap offsets per camera image
     const size_t N = (size_t)X * Y * Z, XY = (size_t)X * Y;
     for (int j0 = 0; j0 < J; j0 += kJointSlice) {
         const VoxJob job{V, min(kJointSlice, J - j0), J, H, W, X, Y, Z, grid_index, cube ? cube + j0 * N : nullptr,
-                         xy ? xy + j0 * XY : nullptr};
+                         xy ? xy + j0 * XY : nullptr, plan};
+        if (plan) plan->j0 = j0;
         const int st = V > 16 ? run_direct<OTF, true>(hm_cl + j0, cp, B, job, src, s)
                               : run_direct<OTF, false>(hm_cl + j0, cp, B, job, src, s);
         if (st != FVP_OK) return st;
@@ -723,13 +791,14 @@ static int check_cl_half(const void *hm_cl, int cp, int J, int H, int W) {
 template <bool OTF>
 static int voxelize_cl_half_any(const _Float16 *hm_cl, int cp, int B, int V, int J, int H, int W,
                                 const CoordSource &src, const int32_t *grid_index, int X, int Y, int Z, float *cube,
-                                float *xy, hipStream_t s) {
+                                float *xy, hipStream_t s, PlanSink *plan = nullptr) {
     const int st0 = check_cl_half(hm_cl, cp, J, H, W);
     if (st0 != FVP_OK) return st0;
     const size_t N = (size_t)X * Y * Z, XY = (size_t)X * Y;
     for (int j0 = 0; j0 < J; j0 += kJointSlice) {
         const VoxJob job{V, min(kJointSlice, J - j0), J, H, W, X, Y, Z, grid_index, cube ? cube + j0 * N : nullptr,
-                         xy ? xy + j0 * XY : nullptr};
+                         xy ? xy + j0 * XY : nullptr, plan};
+        if (plan) plan->j0 = j0;
         const int st = V > 16 ? run_direct_h<OTF, true>(hm_cl + j0, cp, B, job, src, s)
                               : run_direct_h<OTF, false>(hm_cl + j0, cp, B, job, src, s);
         if (st != FVP_OK) return st;
@@ -750,7 +819,17 @@ static int check_args(const void *heatmaps, int B, int V, int J, int H, int W, c
 static size_t workspace_bytes(int B, int V, int J, int H, int W, bool half) {
     if (B <= 0 || V <= 0 || J <= 0 || J > FVP_MAX_JOINTS || H <= 0 || W <= 0) return 0;
     const int J1 = slice_joints(J);  // one joint slice's copy at a time
-    return (size_t)chunk_frames(B, V, J1, H, W, half) * frame_bytes(V, J1, H, W, half);
+    size_t need = (size_t)chunk_frames(B, V, J1, H, W, half) * frame_bytes(V, J1, H, W, half);
+    // a shorter last slice has a narrower copy, so run_chunks fits more frames into the
+    // budget: its chunk can be larger than the first slice's when that one is clipped
+    // (V = 16, 128 x 192, J = 33: 2 frames of 50 MB against 20 of 6.3 MB)
+    // (as run_chunks does, the chunk comes from chunk_frames(.., J2, .., half): for fp16 input and a last slice
+    // of at most 16 joints that is the pair table's frame size and budget, though a sliced call lays every
+    // slice out as fp32 -- safe, the pair frame is the larger of the two, so the chunk is only smaller)
+    const int J2 = J % kJointSlice;
+    if (J > kJointSlice && J2 > 0)
+        need = std::max<size_t>(need, (size_t)chunk_frames(B, V, J2, H, W, half) * cl_frame_bytes(V, J2, H, W));
+    return need;
 }
 
 // -- winners' columns without the cube ----------------------------------------
@@ -1054,6 +1133,47 @@ extern "C" int fvp_voxelize_cl_cams_slab_f16(const void *heatmaps_cl, int cp, in
     return fvp::voxelize_cams_rows(nullptr, false, reinterpret_cast<const float *>(heatmaps_cl), cp, B, V, J, H, W,
                                    cams, grid_index, resize_t, grid, img, x_begin, x_end, cube, xy, nullptr, 0,
                                    (hipStream_t)stream, true);
+}
+
+// The launchers above, walked with a PlanSink in place of the device pointers
+// (never dereferenced on this path): the same argument checks, slices, frame
+// groups, chunks and gather_cfg as the entry point of the kind.
+extern "C" int fvp_voxelize_plan(int kind, int otf, int cp, int B, int V, int J, int H, int W, int X, int Y, int Z,
+                                 int has_grid_index, int cube_aligned, long long *plan, int cap, int *count) {
+    if (!count || (cap > 0 && !plan)) return FVP_ERR_NULL;
+    *count = 0;
+    if (kind < 0 || kind > 3 || cap < 0) return FVP_ERR_SHAPE;
+    fvp::PlanSink sink{plan, cap, 0, 0};
+    // stand-ins with the alignment the checks and the epilogue choice look at
+    const void *hm = reinterpret_cast<const void *>(4096);
+    const float *coords = reinterpret_cast<const float *>(4096);
+    const int32_t *gi = has_grid_index ? reinterpret_cast<const int32_t *>(4096) : nullptr;
+    float *cube = reinterpret_cast<float *>(cube_aligned ? 4096 : 4100), *xy = reinterpret_cast<float *>(4096);
+    void *ws = reinterpret_cast<void *>(4096);
+    int st = fvp::check_args(hm, B, V, J, H, W, coords, X, Y, Z);
+    if (st == FVP_OK && kind == 3) st = fvp::check_cl_half(hm, cp, J, H, W);
+    if (st != FVP_OK) return st;
+    const fvp::CoordSource src{};
+    const auto go = [&](auto o) -> int {
+        constexpr bool OTF = decltype(o)::value;
+        switch (kind) {
+            case 0:
+                return fvp::voxelize_any<OTF, float>(reinterpret_cast<const float *>(hm), B, V, J, H, W, src, gi, X, Y, Z,
+                                                     cube, xy, ws, ~(size_t)0, nullptr, &sink);
+            case 1:
+                return fvp::voxelize_any<OTF, _Float16>(reinterpret_cast<const _Float16 *>(hm), B, V, J, H, W, src, gi, X,
+                                                        Y, Z, cube, xy, ws, ~(size_t)0, nullptr, &sink);
+            case 2:
+                return fvp::voxelize_cl_any<OTF>(reinterpret_cast<const float *>(hm), cp, B, V, J, H, W, src, gi, X, Y, Z,
+                                                 cube, xy, nullptr, &sink);
+            default:
+                return fvp::voxelize_cl_half_any<OTF>(reinterpret_cast<const _Float16 *>(hm), cp, B, V, J, H, W, src, gi,
+                                                      X, Y, Z, cube, xy, nullptr, &sink);
+        }
+    };
+    st = otf ? go(std::true_type{}) : go(std::false_type{});
+    *count = sink.n;
+    return st;
 }
 
 extern "C" int fvp_nchw_to_nhwc_f16(const void *in, int in_half, int N, int C, int H, int W, int Cp, void *out,

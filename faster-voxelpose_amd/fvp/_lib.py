@@ -65,6 +65,7 @@ SIGNATURES = {
     "fvp_voxelize_cl_cams_slab_f16": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                       c_void_p, ctypes.POINTER(GridSpec), ctypes.POINTER(ImageSpec), c_int, c_int,
                                       c_void_p, c_void_p, c_void_p],
+    "fvp_voxelize_plan": [c_int] * 13 + [ctypes.POINTER(ctypes.c_longlong), c_int, ctypes.POINTER(c_int)],
     "fvp_person_planes_cl_f16": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                  ctypes.POINTER(PersonSpec), c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                  c_void_p],

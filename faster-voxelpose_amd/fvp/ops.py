@@ -10,6 +10,7 @@ silently detached.
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 from typing import Optional
 
@@ -333,6 +334,29 @@ def _(heatmaps_cl, J, cams, grid_index, resize_t, start, end, center, bins, ori_
     _, _, X, Y, Z = _x_rows(bins, x_begin, x_end)
     return (heatmaps_cl.new_empty((B, J, X, Y, Z) if want_cube else (0,), dtype=torch.float32),
             heatmaps_cl.new_empty((B, J, X, Y) if want_xy else (0,), dtype=torch.float32))
+
+
+PLAN_KINDS = ("planar_f32", "planar_f16", "cl_f32", "cl_f16")
+GatherLaunch = collections.namedtuple("GatherLaunch", [
+    "j0", "family", "lpv", "jpl", "pair", "casc", "nf", "f0", "nb", "cols", "band", "col_blocks", "sp", "lds",
+    "passes", "vec_full", "vec_last", "status", "blocks", "last_cols", "last_passes", "tab_bytes", "otf", "joints"])
+
+
+def voxelize_plan(kind: str, otf: bool, B: int, V: int, J: int, H: int, W: int, X: int, Y: int, Z: int, cp: int = 0,
+                  grid_index: bool = False, cube_aligned: bool = True) -> tuple[int, list]:
+    """fvp_voxelize_plan (host only): (status, [GatherLaunch, ...]) -- the gather launches
+    the voxelize entry point of `kind` (PLAN_KINDS) would make, in launch order."""
+    n = ctypes.c_int(0)
+    cap = 64
+    while True:
+        buf = (ctypes.c_longlong * (cap * len(GatherLaunch._fields)))()
+        st = _lib.load().fvp_voxelize_plan(PLAN_KINDS.index(kind), int(otf), cp, B, V, J, H, W, X, Y, Z,
+                                           int(grid_index), int(cube_aligned), buf, cap, ctypes.byref(n))
+        if n.value <= cap:
+            break
+        cap = n.value
+    nf = len(GatherLaunch._fields)
+    return st, [GatherLaunch(*buf[i * nf:(i + 1) * nf]) for i in range(n.value)]
 
 
 # ---------------------------------------------------------------------------

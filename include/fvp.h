@@ -195,6 +195,37 @@ int fvp_voxelize_cl_cams_slab_f16(const void *heatmaps_cl, int cp, int B, int V,
                                   const fvp_grid_spec *grid, const fvp_image_spec *img, int x_begin, int x_end,
                                   float *cube, float *xy, void *stream);
 
+/* The gather launches a voxelize call would make (host only; the launcher's
+ * own walk with recording in place of launching, no GPU needed).
+ *   kind  0 planar fp32 (fvp_voxelize / _cams), 1 planar fp16 (fvp_voxelize_f16 /
+ *         _cams with half), 2 channels-last fp32 (fvp_voxelize_cl*), 3 channels-
+ *         last fp16 (fvp_voxelize_cl*_f16);  cp: channels per pixel (kinds 2, 3)
+ *   otf   0 cached packed grid, 1 coordinates projected on the fly (X = the
+ *         launch's x-rows, x_end - x_begin of a slab)
+ *   has_grid_index, cube_aligned: whether grid_index is given, whether the
+ *         cube pointer is 16-B aligned
+ *   plan  host [cap][FVP_VOXELIZE_PLAN_FIELDS], one record per launch in launch
+ *         order; *count = the number of launches (records beyond cap are counted,
+ *         not written)
+ * Returns the status the entry point would return with valid pointers and a
+ * workspace of the required size.  Record fields:
+ *    0 j0: first joint of the slice      1 family: 1 voxelize_kernel,
+ *      2 voxelize_cams_kernel, 3 voxelize_h8_kernel, 4 voxelize_cams_h8_kernel
+ *    2 LPV (lanes per voxel)   3 JPL (joints per lane)   4 PAIR (fp16 pair table)
+ *    5 CASC (V > 16)           6 NF (frames per table entry)
+ *    7 f0, 8 nb: first frame and frames of the launch
+ *    9 cols (voxel columns per block)  10 band (x-rows per band, 0: none)
+ *   11 col_blocks (blocks per frame group)  12 SP (stage pitch, floats)
+ *   13 LDS bytes              14 passes of a full block
+ *   15, 16 vector epilogue on the full blocks / on the last block of a frame
+ *   17 status: FVP_OK, or FVP_ERR_SHAPE for the launch the call fails at (not made)
+ *   18 blocks of the launch   19 columns, 20 passes of the last block
+ *   21 workspace bytes the launch reads (0: heatmaps read in place)
+ *   22 otf                    23 joints of the slice */
+#define FVP_VOXELIZE_PLAN_FIELDS 24
+int fvp_voxelize_plan(int kind, int otf, int cp, int B, int V, int J, int H, int W, int X, int Y, int Z,
+                      int has_grid_index, int cube_aligned, long long *plan, int cap, int *count);
+
 /* Peak NMS + top-K on a [B,1,X,Y] map: 3x3 max-pool keep mask, top-K of the
  * masked map (value descending, flat index ascending on ties), and
  * get_index2D's (flat // X, flat % X) decode.

@@ -130,6 +130,48 @@ def test_conv2d_ex_plan(args, want):
     assert tuple(plan) == want
 
 
+@pytest.mark.parametrize("args, kw, want", [
+    # C2, 8 frames: one chunk, 8 columns of 20 per block in bands of 16 rows, 3 passes, vector epilogue
+    (("planar_f32", False, 8, 5, 15, 128, 240, 80, 80, 20), {},
+     [(0, 1, 4, 4, 0, 0, 1, 0, 8, 8, 16, 800, 164, 10496, 3, 1, 1, 0, 6400, 8, 3, 78643200, 0, 15)]),
+    # C5, 7 fp16 frames on the fly: the pair table at 4, 2 and 1 frames per entry
+    (("planar_f16", True, 7, 31, 15, 128, 240, 160, 160, 64), {},
+     [(0, 2, 4, 4, 1, 1, 4, 0, 4, 2, 16, 12800, 132, 36864, 2, 1, 1, 0, 12800, 2, 2, 244809728, 1, 15),
+      (0, 2, 4, 4, 1, 1, 2, 4, 2, 4, 16, 6400, 260, 36352, 4, 1, 1, 0, 6400, 4, 4, 122404864, 1, 15),
+      (0, 2, 4, 4, 1, 1, 1, 6, 1, 4, 16, 6400, 260, 19712, 4, 1, 1, 0, 6400, 4, 4, 61202432, 1, 15)]),
+    # C4, one frame: 2,048 blocks of 8 columns of 32
+    (("planar_f32", False, 1, 5, 15, 128, 240, 128, 128, 32), {},
+     [(0, 1, 4, 4, 0, 0, 1, 0, 1, 8, 16, 2048, 260, 16640, 4, 1, 1, 0, 2048, 8, 4, 9830400, 0, 15)]),
+    # fp16 channels-last, 40 joints: slices at 4 and 1 lanes per voxel, a short last band, scalar epilogue
+    (("cl_f16", False, 2, 5, 40, 48, 64, 72, 60, 3), {"cp": 48, "cube_aligned": False},
+     [(0, 3, 4, 8, 0, 0, 1, 0, 2, 20, 16, 216, 64, 8192, 1, 0, 0, 0, 432, 20, 1, 0, 0, 32),
+      (32, 3, 1, 8, 0, 0, 1, 0, 2, 60, 16, 72, 184, 5888, 1, 0, 0, 0, 144, 60, 1, 0, 0, 8)]),
+])
+def test_voxelize_plan(args, kw, want):
+    """fvp_voxelize_plan (host only): one record per gather launch, in launch order (the fields of
+    fvp.ops.GatherLaunch); an additive export, the ABI version stays 22.  tests/test_voxelize_plan_model.py
+    sweeps it against an independent model of the rules."""
+    from fvp import _lib, ops
+
+    assert _lib.load().fvp_abi_version() == 22
+    st, recs = ops.voxelize_plan(*args, **kw)
+    assert st == 0 and [tuple(r) for r in recs] == want
+    assert ops.voxelize_plan("planar_f32", False, 0, 5, 15, 128, 240, 80, 80, 20) == (1002, [])
+
+
+def test_voxelize_workspace_covers_a_shorter_last_joint_slice():
+    """33 joints: the 1-joint slice's copy is an eighth of the 32-joint slice's, so its chunk holds 20 frames
+    where the first slice's holds 2 -- the workspace is the larger of the two chunks."""
+    from fvp import _lib, ops
+
+    lib = _lib.load()
+    per32 = 16 * 128 * 192 * 32 * 4
+    assert lib.fvp_voxelize_workspace_bytes(2, 16, 33, 128, 192) == 2 * per32
+    assert lib.fvp_voxelize_workspace_bytes(25, 16, 33, 128, 192) == 20 * (per32 // 8) > 2 * per32
+    st, recs = ops.voxelize_plan("planar_f32", False, 25, 16, 33, 128, 192, 10, 9, 4)
+    assert st == 0 and max(r.tab_bytes for r in recs) == 20 * (per32 // 8)
+
+
 def test_ops_refuse_cpu_tensors():
     from fvp import ops  # noqa: F401  (registers torch.ops.fvp.*)
 

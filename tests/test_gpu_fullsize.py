@@ -117,6 +117,9 @@ def test_c5_full_size_frame_groups(gpu_device):
     w, layer, cams, seq = _layer("c5", gpu_device, True)
     rt = torch.as_tensor(geometry.resize_transform(w.ori_image_size, w.image_size), dtype=torch.float).to(gpu_device)
     hm = torch.from_numpy(synthetic.gaussian_heatmaps(w, 7, first_frame=5).astype(np.float16)).to(gpu_device)
+    from fvp import ops
+    st, plan = ops.voxelize_plan("planar_f16", True, *hm.shape, *w.voxels_per_axis)
+    assert st == 0 and [(r.nf, r.f0, r.nb, r.pair) for r in plan] == [(4, 0, 4, 1), (2, 4, 2, 1), (1, 6, 1, 1)], plan
     cube, xy = layer.forward_fused(hm, {"seq": [seq] * 7}, cams, rt)
     for b in range(7):
         c1, x1 = layer.forward_fused(hm[b:b + 1], {"seq": [seq]}, cams, rt)

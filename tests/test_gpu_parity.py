@@ -213,6 +213,10 @@ def test_ragged_shapes_vs_oracle(gpu_device, bins, J, hm_size):
     trans = geometry.resize_transform(w.ori_image_size, w.image_size)
     rt = torch.as_tensor(trans, dtype=torch.float)
     hm = synthetic.uniform_heatmaps(w, 2, seed=5)
+    from fvp import ops
+    st, plan = ops.voxelize_plan("planar_f32", False, *hm.shape, *bins)
+    # small grids: one-pass blocks, never snapped or banded, one launch per 32-joint slice
+    assert st == 0 and all(r.band == 0 and r.passes == 1 and r.nb == 2 for r in plan) and len(plan) == 1, plan
     cube, xy = layer.forward_fused(hm.to(gpu_device), {"seq": [seq] * 2}, cams, rt.to(gpu_device))
     grid = O.compute_grid(w.space_size, w.space_center, bins)
     sg = np.stack([O.project_grid(grid, c, w.ori_image_size, w.image_size, hm_size, rt.numpy())
@@ -229,8 +233,11 @@ def test_ragged_shapes_vs_oracle(gpu_device, bins, J, hm_size):
 def test_camera_and_joint_counts_vs_oracle(gpu_device, V, J, half, otf):
     """Every lane-group size (J -> 1/2/4/8 lanes per voxel), odd/even and
     >2*LPV camera counts (packed-grid groups), the fp16 pixel-pair table
-    (J <= 16), the fp16 -> fp32 layout fallback (J > 16), and the cached-grid
-    and on-the-fly-projection coordinate sources."""
+    (J <= 16, here at 2 frames and 1 frame per entry), the fp16 -> fp32 layout
+    fallback (J > 16), and the cached-grid and on-the-fly-projection coordinate
+    sources -- each asserted from the launch plan (fvp_voxelize_plan).  The
+    camera counts stay below two complete 16-camera blocks and every launch has
+    one block shape; tests/test_gpu_voxelize_routes.py covers the rest."""
     from fvp import geometry, synthetic
     from fvp.project_whole import ProjectLayer
 
@@ -244,6 +251,13 @@ def test_camera_and_joint_counts_vs_oracle(gpu_device, V, J, half, otf):
     hm = synthetic.uniform_heatmaps(w, 3, seed=V * 100 + J)
     if half:
         hm = hm.half()
+    from fvp import ops
+    st, plan = ops.voxelize_plan("planar_f16" if half else "planar_f32", otf, *hm.shape, *bins)
+    pair = half and J <= 16
+    lpv = 4 if pair else 1 if J <= 4 else 2 if J <= 8 else 4 if J <= 16 else 8
+    assert st == 0 and {(r.family, r.lpv, r.pair, r.casc) for r in plan} == {(2 if otf else 1, lpv, int(pair),
+                                                                              int(V > 16))}, plan
+    assert [r.nf for r in plan] == ([2, 1] if pair else [1]), plan   # 3 frames: a pair and a single, or one launch
     cube, xy = layer.forward_fused(hm.to(gpu_device), {"seq": [seq] * 3}, cams, rt.to(gpu_device))
     grid = O.compute_grid(w.space_size, w.space_center, bins)
     sg = np.stack([O.project_grid(grid, c, w.ori_image_size, w.image_size, hm_size, rt.numpy())
