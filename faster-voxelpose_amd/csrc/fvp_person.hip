@@ -483,12 +483,88 @@ static int person_xsplit(int P, int SY) {
     return rows >= 4096 ? 1 : rows >= 1024 ? 2 : 4;
 }
 
+// heatmaps: planar [B][V][J][H][W] (cp == 0: re-laid out into the workspace
+// first) or channels-last [B][V][H][W][cp] (read in place, no workspace).
+// More than kPersonSlice joints run in joint slices (layout + launch each).
+constexpr int kPersonSlice = 32;
+
+// Every host decision of a per-person call: what person_planes_any launches and
+// what fvp_person_plan reports (one PersonLaunch per joint slice, in launch order).
+struct PersonLaunch {
+    int j0, Jc;          // the slice's first joint and joint count
+    int lpv;             // lanes per voxel (the kernel's LPV; 64 * lpv threads per block)
+    unsigned pix_bytes;  // bytes of one channels-last pixel as the kernel reads it
+};
+struct PersonPlan {
+    int jpl;             // joints per lane: 4 (fp32 pixels), 8 (fp16 pixels)
+    int otf, casc;       // coordinates projected on the fly; 16-camera cascade (V > 16)
+    int xsplit, zsplit;  // blocks per row along x; 64-deep z chunks
+    int xy_direct;       // xy maxima from LDS as plain stores (otherwise atomicMax)
+    int layout;          // a layout pass per slice (planar input)
+    int zeroed_planes;   // planes pre-zeroed by the call: 0 (no planes), 2 or 3 (x split: yz too)
+    unsigned blocks;     // grid of every launch
+    int n;               // launches
+    PersonLaunch s[(FVP_MAX_JOINTS + kPersonSlice - 1) / kPersonSlice];
+};
+
+// The checks an entry point makes on its own arguments before the common ones.
+static int person_entry_check(bool cl, bool cl_half, int cp, int J, bool hm_aligned) {
+    if (cl_half) return (cp <= 0 || cp % 8 || cp < J || J > FVP_MAX_JOINTS || !hm_aligned) ? FVP_ERR_SHAPE : FVP_OK;
+    if (cl) return cp <= 0 ? FVP_ERR_SHAPE : FVP_OK;
+    return FVP_OK;
+}
+
+// The argument checks (all but the null-pointer and workspace checks) and the
+// launch decisions of person_planes_any.  P <= 0 is FVP_OK with no launch.
+static int person_plan(bool otf, int cp, bool cl_half, bool hm_aligned, int B, int V, int J, int H, int W,
+                       const int32_t *bins, const int32_t *fine, int P, bool planes, PersonPlan &pl) {
+    pl = PersonPlan{};
+    if (P <= 0) return FVP_OK;
+    if (B <= 0 || V <= 0 || V > FVP_MAX_VIEWS || J <= 0 || J > FVP_MAX_JOINTS || H < 2 || W < 2) return FVP_ERR_SHAPE;
+    if (otf && V > 64) return FVP_ERR_SHAPE;  // camera records staged in LDS
+    const int SX = bins[0], SY = bins[1], SZ = bins[2];
+    if (SX <= 0 || SY <= 0 || SZ <= 0 || SX > 4096 || SY > 4096 || SZ > 4096 || fine[0] <= 1 || fine[1] <= 1 ||
+        fine[2] <= 1)
+        return FVP_ERR_SHAPE;
+    if (planes && !(SX == SY && SY == SZ)) return FVP_ERR_SHAPE;  // torch.cat of the planes needs a cubic volume
+    // packed fine grid addressed with 32-bit byte offsets
+    if (!otf && (long long)fine[0] * fine[1] * fine[2] * FVP_GRID_SLOTS(V) * 8 > 0xfffff000LL) return FVP_ERR_SHAPE;
+    if (cl_half) {  // fp16 pixels, cp in fp16 elements (as fvp_voxelize_cl_f16); cached fine grid only
+        if (otf || cp <= 0 || cp % 8 || cp < J || !hm_aligned || (unsigned long long)H * W * cp * 2 > 0x7fffffffull)
+            return FVP_ERR_SHAPE;
+    } else if (cp) {
+        const int jl = ((J - 1) / kPersonSlice) * kPersonSlice;
+        if (cp % 4 || cp < jl + 4 * lanes_per_voxel(J - jl) || (size_t)H * W * cp * 4 > 0x7fffffffull)
+            return FVP_ERR_SHAPE;
+    }
+    pl.jpl = cl_half ? 8 : 4;
+    pl.otf = otf ? 1 : 0;
+    pl.casc = V > 16 ? 1 : 0;
+    pl.xsplit = person_xsplit(P, SY);
+    pl.zsplit = (SZ + 63) / 64;
+    // xy maxima stored by their row's block without atomics (person_cl_kernel
+    // xy_direct): one x part, one z chunk, S <= 64 and every joint slice at <= 4
+    // lanes per voxel
+    pl.xy_direct = (planes && pl.xsplit == 1 && SZ <= 64 && SX <= 64 && (J <= 16 || cl_half)) ? 1 : 0;
+    pl.layout = (!cl_half && !cp) ? 1 : 0;
+    // xy, xz (and yz when x is split) hold maxima over non-negative floats: from +0
+    pl.zeroed_planes = planes ? (pl.xsplit > 1 ? 3 : 2) : 0;
+    pl.blocks = (unsigned)((long long)P * SY * pl.xsplit * pl.zsplit);
+    for (int j0 = 0; j0 < J; j0 += kPersonSlice) {
+        PersonLaunch &l = pl.s[pl.n++];
+        l.j0 = j0;
+        l.Jc = J - j0 < kPersonSlice ? J - j0 : kPersonSlice;
+        l.lpv = cl_half ? lanes_per_voxel_h(l.Jc) : lanes_per_voxel(l.Jc);
+        l.pix_bytes = cl_half ? 2u * (unsigned)cp : 4u * (unsigned)(cp ? cp : 4 * l.lpv);
+    }
+    return FVP_OK;
+}
+
 template <int LPV, bool OTF, bool CASC, int JPL = 4>
 static void launch_person_cl(const float *cl, const float *fgrid, const PersonCoords &pc, const float *props,
                              const int32_t *frame_of, const fvp_person_spec &s, float *cubes, float *planes,
                              float *offset, int P, int V, int J, int Jst, int H, int W, unsigned pix_bytes,
-                             int xy_direct, hipStream_t st) {
-    const int SY = s.bins[1];
+                             const PersonPlan &pl, hipStream_t st) {
     // one y-row per block: with the planes-only fast path for x-planes outside the
     // window, rows are the finer and better balanced unit -- measured (C3, 320
     // proposals): 1 row 6.24, 2 rows 6.85, 4 rows 7.4, 8 rows 8.8 us per proposal
@@ -499,8 +575,8 @@ static void launch_person_cl(const float *cl, const float *fgrid, const PersonCo
     // pre-zeroed plane).  Cubes deeper than 64 run as 64-deep z chunks, one block
     // each (the xy and xz maxima combine across blocks through atomics; yz is per
     // (y, z)).
-    const int xmap = 1, xsplit = person_xsplit(P, SY), zsplit = (s.bins[2] + 63) / 64;
-    const dim3 grid((unsigned)((long long)P * SY * xsplit * zsplit));
+    const int xmap = 1, xsplit = pl.xsplit, zsplit = pl.zsplit, xy_direct = pl.xy_direct;
+    const dim3 grid(pl.blocks);
     if constexpr (JPL == 8)
         hipLaunchKernelGGL((person_cl_h8_kernel<LPV, CASC>), grid, dim3(64 * LPV), 0, st, cl, fgrid, pc, props, frame_of,
                            s, cubes, planes, offset, P, V, J, Jst, H, W, xmap, xsplit, zsplit, pix_bytes, xy_direct);
@@ -534,11 +610,6 @@ extern "C" size_t fvp_person_workspace_bytes(int B, int V, int J, int H, int W) 
 
 namespace fvp {
 
-// heatmaps: planar [B][V][J][H][W] (cp == 0: re-laid out into the workspace
-// first) or channels-last [B][V][H][W][cp] (read in place, no workspace).
-// More than kPersonSlice joints run in joint slices (layout + launch each).
-constexpr int kPersonSlice = 32;
-
 static int person_planes_any(const float *heatmaps, int cp, int B, int V, int J, int H, int W,
                              const float *fine_grid, const PersonCoords *pc, const fvp_person_spec *spec,
                              const float *proposals, const int32_t *frame_of, int P, float *cubes, float *planes,
@@ -547,60 +618,41 @@ static int person_planes_any(const float *heatmaps, int cp, int B, int V, int J,
     if (!heatmaps || !spec || (!fine_grid && !pc)) return FVP_ERR_NULL;
     if (P <= 0) return FVP_OK;
     if (!proposals) return FVP_ERR_NULL;
-    if (B <= 0 || V <= 0 || V > FVP_MAX_VIEWS || J <= 0 || J > FVP_MAX_JOINTS || H < 2 || W < 2) return FVP_ERR_SHAPE;
-    if (pc && V > 64) return FVP_ERR_SHAPE;  // camera records staged in LDS
-    const int SX = spec->bins[0], SY = spec->bins[1], SZ = spec->bins[2];
-    if (SX <= 0 || SY <= 0 || SZ <= 0 || SX > 4096 || SY > 4096 || SZ > 4096 || spec->fine[0] <= 1 ||
-        spec->fine[1] <= 1 || spec->fine[2] <= 1)
-        return FVP_ERR_SHAPE;
-    if (planes && !(SX == SY && SY == SZ)) return FVP_ERR_SHAPE;  // torch.cat of the planes needs a cubic volume
-    // packed fine grid addressed with 32-bit byte offsets
-    if (!pc && (long long)spec->fine[0] * spec->fine[1] * spec->fine[2] * FVP_GRID_SLOTS(V) * 8 > 0xfffff000LL)
-        return FVP_ERR_SHAPE;
-    const int J1 = J < kPersonSlice ? J : kPersonSlice;
-    if (cl_half) {  // fp16 pixels, cp in fp16 elements (as fvp_voxelize_cl_f16); cached fine grid only
-        if (pc || cp <= 0 || cp % 8 || cp < J || ((unsigned long long)heatmaps & 15ull) != 0 ||
-            (unsigned long long)H * W * cp * 2 > 0x7fffffffull)
-            return FVP_ERR_SHAPE;
-    } else if (cp) {
-        const int jl = ((J - 1) / kPersonSlice) * kPersonSlice;
-        if (cp % 4 || cp < jl + 4 * lanes_per_voxel(J - jl) || (size_t)H * W * cp * 4 > 0x7fffffffull)
-            return FVP_ERR_SHAPE;
-    } else {
-        const size_t need = (size_t)B * cl_frame_bytes(V, J1, H, W);
+    PersonPlan pl;
+    const int sc = person_plan(pc != nullptr, cp, cl_half, ((unsigned long long)heatmaps & 15ull) == 0, B, V, J, H, W,
+                               spec->bins, spec->fine, P, planes != nullptr, pl);
+    if (sc != FVP_OK) return sc;
+    if (pl.layout) {
+        const size_t need = (size_t)B * cl_frame_bytes(V, pl.s[0].Jc, H, W);
         if (!workspace || workspace_bytes < need) return FVP_ERR_WORKSPACE;
     }
     hipStream_t st = (hipStream_t)stream;
-    // xy maxima stored by their row's block without atomics (person_cl_kernel
-    // xy_direct): one x part, one z chunk, S <= 64 and every joint slice at <= 4
-    // lanes per voxel
-    const int xsplit = person_xsplit(P, SY);
-    const int xy_direct = (planes && xsplit == 1 && SZ <= 64 && SX <= 64 && (J <= 16 || cl_half)) ? 1 : 0;
-    if (planes) {  // xy, xz (and yz when x is split) hold maxima over non-negative floats: from +0
-        const size_t n = (xsplit > 1 ? 3 : 2) * (size_t)P * J * SX * SY;
+    const int SX = spec->bins[0], SY = spec->bins[1], SZ = spec->bins[2];
+    if (pl.zeroed_planes) {
+        const size_t n = pl.zeroed_planes * (size_t)P * J * SX * SY;
         const hipError_t e = hipMemsetAsync(planes, 0, n * 4, st);
         if (e != hipSuccess) return (int)e;
     }
     const PersonCoords none{};
     const PersonCoords &c = pc ? *pc : none;
     const size_t HW = (size_t)H * W, S2 = (size_t)SX * SY, S3 = S2 * SZ;
-    for (int j0 = 0; j0 < J; j0 += kPersonSlice) {
-        const int Jc = J - j0 < kPersonSlice ? J - j0 : kPersonSlice;
+    for (int k = 0; k < pl.n; ++k) {
+        const int j0 = pl.s[k].j0, Jc = pl.s[k].Jc;
+        const unsigned pix_bytes = pl.s[k].pix_bytes;
+        float *cb = cubes ? cubes + j0 * S3 : nullptr;
+        float *pp = planes ? planes + j0 * S2 : nullptr;
         if (cl_half) {
             const float *clh = reinterpret_cast<const float *>(reinterpret_cast<const _Float16 *>(heatmaps) + j0);
-            const unsigned pixb = 2u * (unsigned)cp;
-            float *cb = cubes ? cubes + j0 * S3 : nullptr;
-            float *pl = planes ? planes + j0 * S2 : nullptr;
             auto go = [&](auto lpv) {
                 constexpr int L = decltype(lpv)::value;
-                if (V > 16)
-                    launch_person_cl<L, false, true, 8>(clh, fine_grid, c, proposals, frame_of, *spec, cb, pl, offset, P,
-                                                        V, Jc, J, H, W, pixb, xy_direct, st);
+                if (pl.casc)
+                    launch_person_cl<L, false, true, 8>(clh, fine_grid, c, proposals, frame_of, *spec, cb, pp, offset, P,
+                                                        V, Jc, J, H, W, pix_bytes, pl, st);
                 else
-                    launch_person_cl<L, false, false, 8>(clh, fine_grid, c, proposals, frame_of, *spec, cb, pl, offset,
-                                                         P, V, Jc, J, H, W, pixb, xy_direct, st);
+                    launch_person_cl<L, false, false, 8>(clh, fine_grid, c, proposals, frame_of, *spec, cb, pp, offset,
+                                                         P, V, Jc, J, H, W, pix_bytes, pl, st);
             };
-            switch (lanes_per_voxel_h(Jc)) {
+            switch (pl.s[k].lpv) {
                 case 1: go(std::integral_constant<int, 1>{}); break;
                 case 2: go(std::integral_constant<int, 2>{}); break;
                 default: go(std::integral_constant<int, 4>{}); break;
@@ -608,25 +660,23 @@ static int person_planes_any(const float *heatmaps, int cp, int B, int V, int J,
             continue;
         }
         const float *cl = cp ? heatmaps + j0 : reinterpret_cast<const float *>(workspace);
-        const unsigned pix_bytes = 4u * (unsigned)(cp ? cp : 4 * lanes_per_voxel(Jc));
-        float *cb = cubes ? cubes + j0 * S3 : nullptr;
-        float *pl = planes ? planes + j0 * S2 : nullptr;
 #define FVP_PERSON_CASE(L)                                                                                            \
-    if (!cp) launch_layout<L, float>(heatmaps + j0 * HW, B, V, Jc, J, H, W, reinterpret_cast<float *>(workspace), st); \
-    if (pc && V > 16)                                                                                                 \
-        launch_person_cl<L, true, true>(cl, nullptr, c, proposals, frame_of, *spec, cb, pl, offset, P, V, Jc, J, H,   \
-                                        W, pix_bytes, xy_direct, st);                                                            \
-    else if (pc)                                                                                                      \
-        launch_person_cl<L, true, false>(cl, nullptr, c, proposals, frame_of, *spec, cb, pl, offset, P, V, Jc, J, H,  \
-                                         W, pix_bytes, xy_direct, st);                                                           \
-    else if (V > 16)                                                                                                  \
-        launch_person_cl<L, false, true>(cl, fine_grid, c, proposals, frame_of, *spec, cb, pl, offset, P, V, Jc, J,   \
-                                         H, W, pix_bytes, xy_direct, st);                                                        \
+    if (pl.layout)                                                                                                    \
+        launch_layout<L, float>(heatmaps + j0 * HW, B, V, Jc, J, H, W, reinterpret_cast<float *>(workspace), st);      \
+    if (pl.otf && pl.casc)                                                                                            \
+        launch_person_cl<L, true, true>(cl, nullptr, c, proposals, frame_of, *spec, cb, pp, offset, P, V, Jc, J, H,   \
+                                        W, pix_bytes, pl, st);                                                        \
+    else if (pl.otf)                                                                                                  \
+        launch_person_cl<L, true, false>(cl, nullptr, c, proposals, frame_of, *spec, cb, pp, offset, P, V, Jc, J, H,  \
+                                         W, pix_bytes, pl, st);                                                       \
+    else if (pl.casc)                                                                                                 \
+        launch_person_cl<L, false, true>(cl, fine_grid, c, proposals, frame_of, *spec, cb, pp, offset, P, V, Jc, J,   \
+                                         H, W, pix_bytes, pl, st);                                                    \
     else                                                                                                              \
-        launch_person_cl<L, false, false>(cl, fine_grid, c, proposals, frame_of, *spec, cb, pl, offset, P, V, Jc, J,  \
-                                          H, W, pix_bytes, xy_direct, st);                                                       \
+        launch_person_cl<L, false, false>(cl, fine_grid, c, proposals, frame_of, *spec, cb, pp, offset, P, V, Jc, J,  \
+                                          H, W, pix_bytes, pl, st);                                                   \
     break;
-        switch (lanes_per_voxel(Jc)) {
+        switch (pl.s[k].lpv) {
             case 1: FVP_PERSON_CASE(1)
             case 2: FVP_PERSON_CASE(2)
             case 4: FVP_PERSON_CASE(4)
@@ -638,6 +688,37 @@ static int person_planes_any(const float *heatmaps, int cp, int B, int V, int J,
 }
 
 }  // namespace fvp
+
+// What person_planes_any would do for these arguments (person_plan, the function
+// the launcher itself calls): no device pointer, no HIP call.  (The struct checks of
+// fvp_person_planes_cams -- image size, fine bins -- are not among its inputs.)
+extern "C" int fvp_person_plan(int kind, int cp, int B, int V, int J, int H, int W, int SX, int SY, int SZ, int FX,
+                               int FY, int FZ, int P, int want_cubes, int want_planes, int hm_aligned, long long *plan,
+                               int cap, int *count) {
+    if (!count || (cap > 0 && !plan)) return FVP_ERR_NULL;
+    *count = 0;
+    if (kind < 0 || kind > 3 || cap < 0) return FVP_ERR_SHAPE;
+    (void)want_cubes;  // the cubes change nothing on the host (planes-only blocks walk less: a kernel decision)
+    const bool cl = kind == 2, cl_half = kind == 3;
+    int st = fvp::person_entry_check(cl, cl_half, cp, J, hm_aligned != 0);
+    if (st != FVP_OK) return st;
+    const int32_t bins[3] = {SX, SY, SZ}, fine[3] = {FX, FY, FZ};
+    fvp::PersonPlan pl;
+    st = fvp::person_plan(kind == 1, (cl || cl_half) ? cp : 0, cl_half, hm_aligned != 0, B, V, J, H, W, bins, fine, P,
+                          want_planes != 0, pl);
+    if (st != FVP_OK) return st;
+    for (int k = 0; k < pl.n; ++k) {
+        if (k < cap) {
+            const fvp::PersonLaunch &l = pl.s[k];
+            const long long r[FVP_PERSON_PLAN_FIELDS] = {l.j0, l.Jc, l.lpv, pl.jpl, pl.otf, pl.casc, pl.xsplit,
+                                                         pl.zsplit, pl.xy_direct, pl.blocks, 64 * l.lpv, l.pix_bytes,
+                                                         pl.layout, pl.zeroed_planes};
+            for (int f = 0; f < FVP_PERSON_PLAN_FIELDS; ++f) plan[(size_t)k * FVP_PERSON_PLAN_FIELDS + f] = r[f];
+        }
+    }
+    *count = pl.n;
+    return FVP_OK;
+}
 
 extern "C" int fvp_person_planes(const float *heatmaps, int B, int V, int J, int H, int W, const float *fine_grid,
                                  const fvp_person_spec *spec, const float *proposals, const int32_t *frame_of, int P,
@@ -667,7 +748,7 @@ extern "C" int fvp_person_planes_cl(const float *heatmaps_cl, int cp, int B, int
                                     const int32_t *frame_of, int P, float *cubes, float *planes, float *offset,
                                     void *stream) {
     if (!fine_grid) return FVP_ERR_NULL;
-    if (cp <= 0) return FVP_ERR_SHAPE;
+    if (const int sc = fvp::person_entry_check(true, false, cp, J, true)) return sc;
     return fvp::person_planes_any(heatmaps_cl, cp, B, V, J, H, W, fine_grid, nullptr, spec, proposals, frame_of, P,
                                   cubes, planes, offset, nullptr, 0, stream);
 }
@@ -677,8 +758,8 @@ extern "C" int fvp_person_planes_cl_f16(const void *heatmaps_cl, int cp, int B, 
                                         const int32_t *frame_of, int P, float *cubes, float *planes, float *offset,
                                         void *stream) {
     if (!heatmaps_cl || !fine_grid || !spec) return FVP_ERR_NULL;
-    if (cp <= 0 || cp % 8 || cp < J || J > FVP_MAX_JOINTS || ((unsigned long long)heatmaps_cl & 15ull) != 0)
-        return FVP_ERR_SHAPE;
+    if (const int sc = fvp::person_entry_check(false, true, cp, J, ((unsigned long long)heatmaps_cl & 15ull) == 0))
+        return sc;
     return fvp::person_planes_any(reinterpret_cast<const float *>(heatmaps_cl), cp, B, V, J, H, W, fine_grid, nullptr,
                                   spec, proposals, frame_of, P, cubes, planes, offset, nullptr, 0, stream, true);
 }

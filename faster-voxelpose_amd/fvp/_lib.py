@@ -90,6 +90,7 @@ SIGNATURES = {
                                c_void_p],
     "fvp_person_planes_cl": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, ctypes.POINTER(PersonSpec),
                              c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    "fvp_person_plan": [c_int] * 17 + [ctypes.POINTER(ctypes.c_longlong), c_int, ctypes.POINTER(c_int)],
     "fvp_max_planes": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
     "fvp_soft_argmax": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p],
     "fvp_fuse_poses": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p],

@@ -699,6 +699,27 @@ def _(heatmaps, fine_grid, proposals, frame_of, fine, scale, bias, whole_size, i
             heatmaps.new_empty((P, 3)))
 
 
+PERSON_KINDS = ("planar", "cams", "cl", "cl_f16")
+PersonLaunch = collections.namedtuple("PersonLaunch", [
+    "j0", "jc", "lpv", "jpl", "otf", "casc", "xsplit", "zsplit", "xy_direct", "blocks", "threads", "pix_bytes",
+    "layout", "zeroed_planes"])
+
+
+def person_plan(kind: str, B: int, V: int, J: int, H: int, W: int, bins, fine, P: int, want_cubes: bool = True,
+                want_planes: bool = False, cp: int = 0, aligned: bool = True) -> tuple[int, list]:
+    """fvp_person_plan (host only): (status, [PersonLaunch, ...]) -- the launches the per-person
+    entry point of `kind` (PERSON_KINDS) would make, one per joint slice, in launch order."""
+    n = ctypes.c_int(0)
+    nf = len(PersonLaunch._fields)
+    cap = 32
+    buf = (ctypes.c_longlong * (cap * nf))()
+    st = _lib.load().fvp_person_plan(PERSON_KINDS.index(kind), cp, B, V, J, H, W, *[int(v) for v in bins],
+                                     *[int(v) for v in fine], P, int(want_cubes), int(want_planes), int(aligned),
+                                     buf, cap, ctypes.byref(n))
+    assert n.value <= cap  # FVP_MAX_JOINTS / 32 slices
+    return st, [PersonLaunch(*buf[i * nf:(i + 1) * nf]) for i in range(n.value)]
+
+
 @_custom_op("fvp::max_planes", mutates_args=(), device_types="cuda")
 def max_planes(cubes: torch.Tensor) -> torch.Tensor:
     c = _dev_f32(cubes, "cubes")

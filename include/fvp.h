@@ -336,6 +336,38 @@ int fvp_person_planes_cl_f16(const void *heatmaps_cl, int cp, int B, int V, int 
                              const int32_t *frame_of, int P, float *cubes, float *planes, float *offset,
                              void *stream);
 
+/* The launches a per-person call would make (host only: no device pointer, no
+ * HIP call; the decision function the launcher itself calls).
+ *   kind  0 planar fp32 on the cached grid (fvp_person_planes), 1 planar fp32,
+ *         coordinates on the fly (fvp_person_planes_cams), 2 channels-last fp32
+ *         (fvp_person_planes_cl), 3 channels-last fp16 (fvp_person_planes_cl_f16)
+ *   cp    channels per pixel (kinds 2, 3; ignored otherwise)
+ *   SX, SY, SZ  fvp_person_spec.bins;  FX, FY, FZ  fvp_person_spec.fine
+ *   want_cubes, want_planes: whether cubes / planes are non-NULL
+ *   hm_aligned: whether the heatmap pointer is 16-B aligned (looked at by kind 3)
+ *   plan  host [cap][FVP_PERSON_PLAN_FIELDS], one record per launch (joint slice)
+ *         in launch order; *count = the number of launches (records beyond cap
+ *         are counted, not written)
+ * Returns the status the entry point would return with valid pointers and a
+ * workspace of the required size (P <= 0: FVP_OK and no launch).  Not seen by
+ * the query, besides the null-pointer and workspace checks: the two
+ * FVP_ERR_SHAPE checks fvp_person_planes_cams makes on its structs (img->hm_w /
+ * hm_h against W / H, fine_grid_spec->bins against spec->fine).  Record fields:
+ *    0 j0, 1 Jc: first joint and joints of the slice
+ *    2 LPV (lanes per voxel)   3 JPL (joints per lane: 4 fp32, 8 fp16)
+ *    4 OTF                     5 CASC (V > 16)
+ *    6 xsplit (blocks per row along x)    7 zsplit (64-deep z chunks)
+ *    8 xy_direct (xy maxima as plain stores from LDS; 0: atomicMax)
+ *    9 blocks of the launch   10 threads per block
+ *   11 pix_bytes (bytes of one channels-last pixel as the kernel reads it)
+ *   12 layout (1: a layout pass into the workspace precedes the launch)
+ *   13 zeroed_planes (planes the call pre-zeroes: 0, 2, or 3 when x is split;
+ *      the same in every record) */
+#define FVP_PERSON_PLAN_FIELDS 14
+int fvp_person_plan(int kind, int cp, int B, int V, int J, int H, int W, int SX, int SY, int SZ, int FX, int FY,
+                    int FZ, int P, int want_cubes, int want_planes, int hm_aligned, long long *plan, int cap,
+                    int *count);
+
 /* xy / xz / yz max-projections of per-person cubes [P][J][S][S][S] into
  * planes [3P][J][S][S] (xy block first, then xz, then yz).
  * Replaces torch.cat([max(c,4), max(c,3), max(c,2)]) at

@@ -159,6 +159,40 @@ def test_voxelize_plan(args, kw, want):
     assert ops.voxelize_plan("planar_f32", False, 0, 5, 15, 128, 240, 80, 80, 20) == (1002, [])
 
 
+@pytest.mark.parametrize("args, kw, st, want", [
+    # the product's per-frame call: 10 proposals of 64^3, planar, cubes -> 4 x parts, a layout pass, nothing zeroed
+    (("planar", 1, 5, 15, 128, 240, (64,) * 3, (253, 253, 64), 10), {}, 0,
+     [(0, 15, 4, 4, 0, 0, 4, 1, 0, 2560, 256, 64, 1, 0)]),
+    # forward_batch: 64 proposals, planes -> one part per row, xy from LDS, xy and xz pre-zeroed
+    (("planar", 8, 5, 15, 128, 240, (64,) * 3, (253, 253, 64), 64), {"want_cubes": False, "want_planes": True}, 0,
+     [(0, 15, 4, 4, 0, 0, 1, 1, 1, 4096, 256, 64, 1, 2)]),
+    # 17 joints at one part per row: 8 lanes per voxel keep the xy atomics
+    (("cams", 8, 17, 17, 128, 240, (64,) * 3, (253, 253, 64), 64), {"want_planes": True}, 0,
+     [(0, 17, 8, 4, 1, 1, 1, 1, 0, 4096, 512, 128, 1, 2)]),
+    # fp16 channels-last, 40 joints, 96 deep: two slices at 4 and 1 lanes per voxel, 2 x parts, 2 z chunks
+    (("cl_f16", 2, 5, 40, 48, 64, (96,) * 3, (190, 190, 96), 16), {"want_planes": True, "cp": 48}, 0,
+     [(0, 32, 4, 8, 0, 0, 2, 2, 0, 6144, 256, 96, 0, 3), (32, 8, 1, 8, 0, 0, 2, 2, 0, 6144, 64, 96, 0, 3)]),
+    # channels-last fp32 read in place: the pixel is the caller's cp floats
+    (("cl", 1, 5, 15, 48, 64, (8,) * 3, (15,) * 3, 8), {"cp": 16}, 0,
+     [(0, 15, 4, 4, 0, 0, 4, 1, 0, 256, 256, 64, 0, 0)]),
+    (("planar", 1, 5, 15, 48, 64, (8, 8, 4), (15,) * 3, 8), {"want_planes": True}, 1002, []),  # planes, not cubic
+    (("cams", 1, 65, 15, 48, 64, (8,) * 3, (15,) * 3, 8), {}, 1002, []),          # camera records beyond LDS
+    (("cl_f16", 1, 5, 15, 48, 64, (8,) * 3, (15,) * 3, 8), {"cp": 16, "aligned": False}, 1002, []),
+    (("cl_f16", 1, 5, 15, 48, 64, (8,) * 3, (15,) * 3, 0), {"cp": 12}, 1002, []),  # the entry's own check, before P
+    (("cl", 1, 5, 33, 48, 64, (8,) * 3, (15,) * 3, 8), {"cp": 32}, 1002, []),     # cp below the last slice's quads
+    (("planar", 1, 5, 15, 48, 64, (8,) * 3, (15,) * 3, 0), {}, 0, []),            # no proposals: no launch
+])
+def test_person_plan(args, kw, st, want):
+    """fvp_person_plan (host only): one record per launch (joint slice) of a per-person call, in launch order
+    (the fields of fvp.ops.PersonLaunch) -- the decision function the launcher calls; an additive export, the
+    ABI version stays 22.  tests/test_person_cases.py sweeps it against an independent model of the rules."""
+    from fvp import _lib, ops
+
+    assert _lib.load().fvp_abi_version() == 22
+    got, recs = ops.person_plan(*args, **kw)
+    assert got == st and [tuple(r) for r in recs] == want
+
+
 def test_voxelize_workspace_covers_a_shorter_last_joint_slice():
     """33 joints: the 1-joint slice's copy is an eighth of the 32-joint slice's, so its chunk holds 20 frames
     where the first slice's holds 2 -- the workspace is the larger of the two chunks."""

@@ -605,6 +605,12 @@ def test_person_joint_slices_and_deep_cubes(gpu_device, J, S, otf):
     layer.on_the_fly = otf
     pg = torch.from_numpy(props).to(gpu_device)
     meta = {"seq": [seq]}
+    from fvp import ops
+
+    st, plan = ops.person_plan("cams" if otf else "planar", *hm.shape[:2], J, *hm.shape[3:], (S,) * 3,
+                               layer.fine_voxels_per_axis.tolist(), len(props), want_cubes=False, want_planes=True)
+    assert st == 0 and [r.j0 for r in plan] == list(range(0, J, 32)), plan   # the joint slices, the z chunks
+    assert {(r.xsplit, r.zsplit, r.otf, r.zeroed_planes) for r in plan} == {(4, (S + 63) // 64, int(otf), 3)}, plan
     planes, offset = layer.forward_planes(hm, 0, meta, pg, cams, rt)
     cubes, off2 = layer(hm, 0, meta, pg, cams, rt)
     ind = O.Individual(w.space_size, w.space_center, w.ind_space_size, w.ind_voxels_per_axis)
