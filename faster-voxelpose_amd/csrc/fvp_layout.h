@@ -4,6 +4,7 @@
 // range check.
 #pragma once
 
+#include <type_traits>
 #include <utility>
 
 #include "fvp_device.h"
@@ -379,6 +380,201 @@ __device__ __forceinline__ Taps4<PAIR> setup_taps(float gx, float gy, float sxs,
         t.o[3] = (vy1 & vx1) ? p + (unsigned)(W + 1) * unit : kOOB;
     }
     return t;
+}
+
+// -- the camera sum of one voxel ----------------------------------------------------
+// Where the sampling coordinates come from: a packed per-sequence grid
+// (OTF = false), or the camera records, projected on the fly with the exact
+// fp32 sequence of project_grid_kernel (OTF = true; used when the grid would
+// not stay cache-resident, e.g. 31 cameras x 160x160x64 = 420 MB).  The
+// per-person gather samples the fine grid: gs is the fine grid, x_off 0.
+struct CoordSource {
+    const float *grids;     // packed grids [S][N][GV][2]            (!OTF)
+    const float *cams;      // camera records [S][V][FVP_CAM_STRIDE] (OTF)
+    const float *resize_t;  // [2][3]                                (OTF)
+    fvp_grid_spec gs;       // (OTF) the whole grid: x-row i of a launch is row x_off + i of gs
+    ImageConsts im;
+    int x_off;              // (OTF) first x-row of an x-slab launch (0: the whole grid)
+};
+
+struct NoPark {};
+
+// acc[f][m] = the V cameras' bilinear taps of one voxel, summed in the reference's
+// order (fvp_device.h: torch's CPU mean over the views folds complete blocks of 16
+// cameras, CASC = V > 16), before the division; `valid` false gives 0.  A group of
+// LPV lanes shares the voxel: lane q (qo = 16 q, its bytes within a pixel / pair
+// entry) holds joints JPL q .. JPL q + JPL - 1 of the NF frames of a table entry, and
+// sets up cameras v0+2q, v0+2q+1 of each group of 2 LPV, which the group picks up
+// through lane broadcasts -- one grid load and one tap setup per 2 LPV voxel-cameras.
+// Coordinates: the slots of voxel gn of the packed grid behind grs, or the centre
+// (wx, wy, wz) projected through the GV camera records at lcam (LDS) with rt / im.
+// frame_tab: the frame group's per-camera images of img bytes, entries of NF * pix.
+// JPL joints per lane: 4 (a lane's 16 B = 4 fp32 joints, or the pair table's 2 x 4
+// fp16) or 8 (fp16 channels-last pixels read in place: 16 B = 8 fp16 joints, so a
+// voxel needs half the lanes and a wave's four tap loads serve twice the voxels).
+// park (other than NoPark): called as park(v0, sums) at the top of every camera
+// group; the caller keeps the completed 16-camera blocks itself (2 LPV divides 16, so
+// a block only ever completes at a group's first camera), and there is no register
+// fold and no final add here.
+// MODE (replay probe, tools/person_probe.hip; the product instantiates 0): 2 = zeros
+// instead of the tap loads, 3 = every tap offset off-image (range-checked loads, no
+// memory access), 4 = grid loads and tap setup only.
+// INPLACE: the running sums are acc itself instead of a local array copied out at the
+// end.  The arithmetic is the same; the compiler optimises this function before it
+// inlines it, with the sums in registers or behind the reference, and each gather
+// keeps the form its registers were tuned with: the whole-space kernels the local
+// array (in place, three of the 8-joint cascade kernels move by 1-2 VGPRs), the
+// per-person kernels in place (local: person_cl_kernel<2, true, true> 111 VGPRs for
+// 115) -- profiles/gather_sum/.
+template <int LPV, bool PAIR, bool OTF, bool CASC, int NF, int JPL, int MODE = 0, bool INPLACE = false,
+          typename Park = NoPark>
+__device__ __forceinline__ void camera_sum(float (&acc)[NF][JPL], bool valid, long long gn, float wx, float wy,
+                                           float wz, const __amdgpu_buffer_rsrc_t &grs, const float *lcam,
+                                           const float *rt, const ImageConsts &im, const char *frame_tab,
+                                           unsigned img, unsigned pix, unsigned qo, int q, int V, int GV, int W, int H,
+                                           float sxs, float sys, Park park = {}) {
+    static_assert(!PAIR || LPV == 4, "the fp16 pair table has 4 lanes per voxel");
+    static_assert(JPL == 4 || (JPL == 8 && !PAIR && NF == 1), "fp16 channels-last: one frame per pixel, no table");
+    static_assert(MODE == 0 || (!PAIR && NF == 1 && JPL == 4), "the probe modes: fp32 pixels");
+    constexpr bool PARK = !std::is_same<Park, NoPark>::value;
+    constexpr int CPG = 2 * LPV;  // cameras per grid load (2 per lane)
+    const unsigned unit = pix * NF;  // bytes per entry
+    float own[NF][JPL];
+    float (&sum)[NF][JPL] = INPLACE ? acc : own;
+    float blk[NF][JPL];  // blk (CASC): completed 16-camera blocks (view_sum order)
+#pragma unroll
+    for (int f = 0; f < NF; ++f)
+#pragma unroll
+        for (int m = 0; m < JPL; ++m) sum[f][m] = blk[f][m] = 0.0f;
+    for (int v0 = 0; v0 < V; v0 += CPG) {
+        if constexpr (PARK) park(v0, sum);
+        // cameras v0+2q, v0+2q+1 of voxel gn (past V: padding, unused)
+        float g[4];
+        if constexpr (OTF) {
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const Cam c = load_cam(lcam + min(v0 + 2 * q + h, GV - 1) * FVP_CAM_STRIDE);
+                float px, py;
+                project_point(c, wx, wy, wz, px, py);
+                pixel_to_sample(px, py, rt, im, g[2 * h], g[2 * h + 1]);
+            }
+        } else {
+            // slots v0+2q, v0+2q+1 (past the row: the next voxel's or 0)
+            const u32x4 graw = __builtin_amdgcn_raw_buffer_load_b128(grs, (unsigned)((gn * GV + v0 + 2 * q) * 8), 0, 0);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) g[k] = __builtin_bit_cast(float, (unsigned)graw[k]);
+        }
+        // invalid slots sample (-2, -2): off-image, every tap kOOB, contributes exactly 0
+#pragma unroll
+        for (int k = 0; k < 4; ++k) g[k] = valid ? g[k] : -2.0f;
+        const Taps4<PAIR> t0 = setup_taps<PAIR>(g[0], g[1], sxs, sys, W, H, unit);
+        const Taps4<PAIR> t1 = setup_taps<PAIR>(g[2], g[3], sxs, sys, W, H, unit);
+        static_for(std::make_integer_sequence<int, CPG>{}, [&](auto kc) {
+            constexpr int k = decltype(kc)::value;
+            constexpr int S = k >> 1;  // lane of the group that set this camera up
+            const int v = v0 + k;
+            if (v >= V) return;
+            if constexpr (CASC && !PARK) {
+                if ((v & 15) == 0 && v > 0) {  // a block of 16 cameras is complete: fold it (fvp_device.h)
+#pragma unroll
+                    for (int f = 0; f < NF; ++f)
+#pragma unroll
+                        for (int m = 0; m < JPL; ++m) {
+                            blk[f][m] = blk[f][m] + sum[f][m];
+                            sum[f][m] = 0.0f;
+                        }
+                }
+            }
+            const Taps4<PAIR> &src = (k & 1) ? t1 : t0;
+            unsigned o[Taps4<PAIR>::NO];
+            unsigned all = kOOB;
+#pragma unroll
+            for (int m = 0; m < Taps4<PAIR>::NO; ++m) {
+                o[m] = group_bcast<LPV, S>(src.o[m]);
+                all &= o[m];
+            }
+            // whole wave off-image (every tap's kOOB bit set): contributes exactly 0
+            if (!__builtin_amdgcn_ballot_w64((all & kOOB) == 0u)) return;
+            float w[4];
+#pragma unroll
+            for (int m = 0; m < 4; ++m) w[m] = group_bcast<LPV, S>(src.w[m]);
+            if constexpr (MODE == 4) {
+#pragma unroll
+                for (int m = 0; m < 4; ++m) sum[0][m] = sum[0][m] + w[m] + __builtin_bit_cast(float, o[m]);
+                return;
+            }
+            if constexpr (MODE == 3) {
+#pragma unroll
+                for (int m = 0; m < 4; ++m) o[m] = kOOB;
+            }
+            const __amdgpu_buffer_rsrc_t rs = uniform_rsrc(frame_tab + (size_t)v * img, img);
+            if constexpr (PAIR) {
+                // r0 = [a j0 j1 | a j2 j3 | b j0 j1 | b j2 j3] (row y0), r1 likewise (c, d; row y1)
+                u32x4 r0[NF], r1[NF];
+#pragma unroll
+                for (int f = 0; f < NF; ++f) {
+                    r0[f] = __builtin_amdgcn_raw_buffer_load_b128(rs, o[0] + f * pix + qo, 0, 0);
+                    r1[f] = __builtin_amdgcn_raw_buffer_load_b128(rs, o[1] + f * pix + qo, 0, 0);
+                }
+#pragma unroll
+                for (int f = 0; f < NF; ++f)
+                    static_for(std::make_integer_sequence<int, 4>{}, [&](auto mc) {
+                        constexpr int m = decltype(mc)::value, HI = m & 1;
+                        const unsigned ua = r0[f][m >> 1], ub = r0[f][2 + (m >> 1)];
+                        const unsigned uc = r1[f][m >> 1], ud = r1[f][2 + (m >> 1)];
+                        // fd*w3 + (fc*w2 + (fb*w1 + fa*w0)), the fp16 taps converted inside the fmas
+                        const float t = fma_h<HI>(ua, w[0], -0.0f);
+                        sum[f][m] = sum[f][m] + fma_h<HI>(ud, w[3], fma_h<HI>(uc, w[2], fma_h<HI>(ub, w[1], t)));
+                    });
+            } else {
+                u32x4 a[NF], bq[NF], c[NF], d[NF];
+#pragma unroll
+                for (int f = 0; f < NF; ++f) {
+                    if constexpr (MODE == 2) {
+                        a[f] = bq[f] = c[f] = d[f] = u32x4{0u, 0u, 0u, 0u};
+                    } else {
+                        a[f] = __builtin_amdgcn_raw_buffer_load_b128(rs, o[0] + f * pix + qo, 0, 0);
+                        bq[f] = __builtin_amdgcn_raw_buffer_load_b128(rs, o[1] + f * pix + qo, 0, 0);
+                        c[f] = __builtin_amdgcn_raw_buffer_load_b128(rs, o[2] + f * pix + qo, 0, 0);
+                        d[f] = __builtin_amdgcn_raw_buffer_load_b128(rs, o[3] + f * pix + qo, 0, 0);
+                    }
+                }
+                if constexpr (JPL == 8) {
+                    // word i of a pixel piece = joints 8q+2i (low half), 8q+2i+1 (high half):
+                    // fd*w3 + (fc*w2 + (fb*w1 + fa*w0)), the fp16 taps converted inside the fmas
+                    static_for(std::make_integer_sequence<int, 8>{}, [&](auto mc) {
+                        constexpr int m = decltype(mc)::value, HI = m & 1, wd = m >> 1;
+                        const float t = fma_h<HI>(a[0][wd], w[0], -0.0f);
+                        sum[0][m] = sum[0][m] +
+                                    fma_h<HI>(d[0][wd], w[3], fma_h<HI>(c[0][wd], w[2], fma_h<HI>(bq[0][wd], w[1], t)));
+                    });
+                } else {
+#pragma unroll
+                    for (int f = 0; f < NF; ++f)
+#pragma unroll
+                        for (int m = 0; m < 4; ++m) {
+                            const float fa = __builtin_bit_cast(float, (unsigned)a[f][m]);
+                            const float fb = __builtin_bit_cast(float, (unsigned)bq[f][m]);
+                            const float fc = __builtin_bit_cast(float, (unsigned)c[f][m]);
+                            const float fd = __builtin_bit_cast(float, (unsigned)d[f][m]);
+                            sum[f][m] = sum[f][m] + __builtin_fmaf(fd, w[3], __builtin_fmaf(fc, w[2],
+                                                                   __builtin_fmaf(fb, w[1], fa * w[0])));
+                        }
+                }
+            }
+        });
+    }
+    // the sum's final levels (fvp_device.h): remainder + blocks, or + 0 (a -0 sum becomes +0)
+    if constexpr (!PARK) {
+#pragma unroll
+        for (int f = 0; f < NF; ++f)
+#pragma unroll
+            for (int m = 0; m < JPL; ++m) sum[f][m] = sum[f][m] + (CASC ? blk[f][m] : 0.0f);
+    }
+#pragma unroll
+    for (int f = 0; f < NF; ++f)
+#pragma unroll
+        for (int m = 0; m < JPL; ++m) acc[f][m] = sum[f][m];
 }
 
 inline int lanes_per_voxel(int J) { return J <= 4 ? 1 : J <= 8 ? 2 : J <= 16 ? 4 : 8; }

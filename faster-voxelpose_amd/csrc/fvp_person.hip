@@ -133,140 +133,18 @@ __global__ __launch_bounds__(256) void max_planes_generic_kernel(const float *__
 // Sampling coordinates of the fine grid: the packed per-sequence grid
 // (OTF = false) or projected on the fly from the camera records with the fp32
 // sequence of fvp_project_grid (OTF = true: no 197 MB fine grid to stream).
-struct PersonCoords {
-    const float *cams;      // [V][FVP_CAM_STRIDE]   (OTF)
-    const float *resize_t;  // [2][3]                (OTF)
-    fvp_grid_spec fine;     // fine whole-space grid (OTF)
-    ImageConsts im;         //                       (OTF)
-};
-
-// The clamped-mean input of one fine voxel of the person cube: the V cameras'
-// bilinear taps summed in the reference's order (project_individual.py:278-283,
-// fvp_device.h), before the division.  A group of LPV lanes shares the voxel
-// (lane q holds joints 4q..4q+3); `valid` false (outside the window or the
-// cube) gives 0.  Coordinates from the packed fine grid or projected on the fly.
-// JPL = 8: fp16 channels-last pixels, lane q holds joints 8q..8q+7 (fvp_voxelize.hip).
-template <int LPV, bool OTF, bool CASC, int MODE, int JPL = 4>
-__device__ __forceinline__ void person_voxel_sum(float (&acc)[JPL], bool valid, int gx, int gy, int gz,
-                                                 const __amdgpu_buffer_rsrc_t &grs, const float *lcam, const float *rt,
-                                                 const PersonCoords &pc, const fvp_person_spec &s,
-                                                 const char *__restrict__ frame_cl, unsigned img, unsigned qo, int q,
-                                                 int V, int GV, int W, int H, float sxs, float sys,
-                                                 unsigned pix_bytes) {
-    constexpr int CPG = 2 * LPV;  // cameras per packed-grid load (2 per lane)
-#pragma unroll
-    for (int m = 0; m < JPL; ++m) acc[m] = 0.0f;
-    float blk[JPL];  // CASC: completed 16-camera blocks (fvp_device.h)
-#pragma unroll
-    for (int m = 0; m < JPL; ++m) blk[m] = 0.0f;
-    if (__builtin_amdgcn_ballot_w64(valid)) {
-        const long long gn = valid ? ((long long)gx * s.fine[1] + gy) * s.fine[2] + gz : 0;
-        float wxc = 0.f, wyc = 0.f, wzc = 0.f;  // OTF: fine voxel centre (compute_grid at fine resolution)
-        if constexpr (OTF) {
-            wxc = axis_coord(pc.fine.start[0], pc.fine.end[0], s.fine[0], valid ? gx : 0, pc.fine.center[0]);
-            wyc = axis_coord(pc.fine.start[1], pc.fine.end[1], s.fine[1], valid ? gy : 0, pc.fine.center[1]);
-            wzc = axis_coord(pc.fine.start[2], pc.fine.end[2], s.fine[2], valid ? gz : 0, pc.fine.center[2]);
-        }
-        for (int v0 = 0; v0 < V; v0 += CPG) {
-            float g[4];
-            if constexpr (OTF) {
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const Cam c = load_cam(lcam + min(v0 + 2 * q + h, GV - 1) * FVP_CAM_STRIDE);
-                    float px, py;
-                    project_point(c, wxc, wyc, wzc, px, py);
-                    pixel_to_sample(px, py, rt, pc.im, g[2 * h], g[2 * h + 1]);
-                }
-            } else {
-                // slots v0+2q, v0+2q+1 of fine voxel gn (packed grid, fvp_pack_grid)
-                const u32x4 graw =
-                    __builtin_amdgcn_raw_buffer_load_b128(grs, (unsigned)((gn * GV + v0 + 2 * q) * 8), 0, 0);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) g[k] = __builtin_bit_cast(float, (unsigned)graw[k]);
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) g[k] = valid ? g[k] : -2.0f;
-            const Taps4<false> t0 = setup_taps<false>(g[0], g[1], sxs, sys, W, H, pix_bytes);
-            const Taps4<false> t1 = setup_taps<false>(g[2], g[3], sxs, sys, W, H, pix_bytes);
-            static_for(std::make_integer_sequence<int, CPG>{}, [&](auto kc) {
-                constexpr int k = decltype(kc)::value;
-                constexpr int S = k >> 1;
-                const int v = v0 + k;
-                if (v >= V) return;
-                if constexpr (CASC) {
-                    if ((v & 15) == 0 && v > 0) {
-#pragma unroll
-                        for (int m = 0; m < JPL; ++m) {
-                            blk[m] = blk[m] + acc[m];
-                            acc[m] = 0.0f;
-                        }
-                    }
-                }
-                const Taps4<false> &src = (k & 1) ? t1 : t0;
-                unsigned o[4];
-                unsigned all = kOOB;
-#pragma unroll
-                for (int m = 0; m < 4; ++m) {
-                    o[m] = group_bcast<LPV, S>(src.o[m]);
-                    all &= o[m];
-                }
-                if (!__builtin_amdgcn_ballot_w64((all & kOOB) == 0u)) return;
-                float wt[4];
-#pragma unroll
-                for (int m = 0; m < 4; ++m) wt[m] = group_bcast<LPV, S>(src.w[m]);
-                if constexpr (MODE == 4) {
-#pragma unroll
-                    for (int m = 0; m < 4; ++m) acc[m] = acc[m] + wt[m] + __builtin_bit_cast(float, o[m]);
-                    return;
-                }
-                if constexpr (MODE == 3) {
-#pragma unroll
-                    for (int m = 0; m < 4; ++m) o[m] = kOOB;
-                }
-                const __amdgpu_buffer_rsrc_t rs = uniform_rsrc(frame_cl + (size_t)v * img, img);
-                u32x4 ta = {0u, 0u, 0u, 0u}, tb = ta, tc = ta, td = ta;
-                if constexpr (MODE != 2) {
-                    ta = __builtin_amdgcn_raw_buffer_load_b128(rs, o[0] + qo, 0, 0);
-                    tb = __builtin_amdgcn_raw_buffer_load_b128(rs, o[1] + qo, 0, 0);
-                    tc = __builtin_amdgcn_raw_buffer_load_b128(rs, o[2] + qo, 0, 0);
-                    td = __builtin_amdgcn_raw_buffer_load_b128(rs, o[3] + qo, 0, 0);
-                }
-                if constexpr (JPL == 8) {
-                    // word i of a piece = joints 8q+2i (low half), 8q+2i+1 (high half)
-                    static_for(std::make_integer_sequence<int, 8>{}, [&](auto mc) {
-                        constexpr int m = decltype(mc)::value, HI = m & 1, wd = m >> 1;
-                        const float t = fma_h<HI>(ta[wd], wt[0], -0.0f);
-                        acc[m] = acc[m] + fma_h<HI>(td[wd], wt[3], fma_h<HI>(tc[wd], wt[2], fma_h<HI>(tb[wd], wt[1], t)));
-                    });
-                    return;
-                }
-#pragma unroll
-                for (int m = 0; m < 4; ++m) {
-                    const float fa = __builtin_bit_cast(float, (unsigned)ta[m]);
-                    const float fb = __builtin_bit_cast(float, (unsigned)tb[m]);
-                    const float fc = __builtin_bit_cast(float, (unsigned)tc[m]);
-                    const float fd = __builtin_bit_cast(float, (unsigned)td[m]);
-                    acc[m] = acc[m] + __builtin_fmaf(fd, wt[3], __builtin_fmaf(fc, wt[2],
-                                                                              __builtin_fmaf(fb, wt[1], fa * wt[0])));
-                }
-            });
-        }
-    }
-    // the sum's final levels (fvp_device.h): remainder + blocks, or + 0 (a -0 sum becomes +0)
-#pragma unroll
-    for (int m = 0; m < JPL; ++m) acc[m] = acc[m] + (CASC ? blk[m] : 0.0f);
-}
-
+// (CoordSource, fvp_layout.h, with gs the fine grid; the kernels take the packed fine grid
+// as an argument of its own, fgrid: read through the struct, person_cl_h8_kernel<1, true>
+// needs 75 VGPRs instead of 72 and loses an occupancy step.)
 // MODE (replay probe, tools/person_probe.hip; the product launches 0): 1 = no
-// plane reductions / stores (the sums folded into `offset`), 2 = zeros instead
-// of the tap loads, 3 = every tap offset off-image (range-checked loads, no
-// memory access), 4 = grid loads and tap setup only (no tap loads, no planes),
+// plane reductions / stores (the sums folded into `offset`), 2 / 3 / 4 = inside the
+// camera sum (camera_sum, fvp_layout.h; 4 also without the planes),
 // 5 / 6 = no xz / xy plane atomics or stores, 7 = xz atomics from even z lanes only,
 // 8 = plain stores instead of the xz atomics (timing only: wrong maxima).
 // JPL joints per lane: 4 (fp32 pixels) or 8 (fp16 pixels, JP = 8 * LPV joints per block).
 template <int LPV, bool OTF, bool CASC, int MODE, int JPL>
 __device__ __forceinline__ void person_cl_body(const float *__restrict__ cl,
-                                               const float *__restrict__ fgrid, const PersonCoords &pc,
+                                               const float *__restrict__ fgrid, const CoordSource &src,
                                                const float *__restrict__ props,
                                                const int32_t *__restrict__ frame_of, const fvp_person_spec &s,
                                                float *__restrict__ cubes, float *__restrict__ planes,
@@ -313,9 +191,9 @@ __device__ __forceinline__ void person_cl_body(const float *__restrict__ cl,
     float rt[6];
     if constexpr (OTF) {
         for (int e = threadIdx.x; e < GV * FVP_CAM_STRIDE; e += 64 * LPV)
-            lcam[e] = e < V * FVP_CAM_STRIDE ? pc.cams[e] : 0.0f;
+            lcam[e] = e < V * FVP_CAM_STRIDE ? src.cams[e] : 0.0f;
 #pragma unroll
-        for (int k = 0; k < 6; ++k) rt[k] = pc.resize_t[k];
+        for (int k = 0; k < 6; ++k) rt[k] = src.resize_t[k];
         __syncthreads();
     } else {
         grs = uniform_rsrc(fgrid, (unsigned)(FN * GV * 8));
@@ -366,19 +244,33 @@ __device__ __forceinline__ void person_cl_body(const float *__restrict__ cl,
         const int gx = w.ctl[0] + x;
         const bool xin = !w.skip && gx >= w.start[0] && gx < w.end[0];
         const bool valid = xin && zin && row_in;
-        float acc[JPL];
-        person_voxel_sum<LPV, OTF, CASC, MODE, JPL>(acc, valid, gx, gy, gz, grs, lcam, rt, pc, s, frame_cl, img, qo, q, V, GV,
-                                               W, H, sxs, sys, pix_bytes);
+        // the clamped-mean input of fine voxel (gx, gy, gz): the V cameras' taps summed in the
+        // reference's order (project_individual.py:278-283); outside the window or the cube: 0
+        float acc[1][JPL];
+#pragma unroll
+        for (int k = 0; k < JPL; ++k) acc[0][k] = 0.0f;
+        if (__builtin_amdgcn_ballot_w64(valid)) {
+            const long long gn = valid ? ((long long)gx * s.fine[1] + gy) * s.fine[2] + gz : 0;
+            float wxc = 0.f, wyc = 0.f, wzc = 0.f;  // OTF: fine voxel centre (compute_grid at fine resolution)
+            if constexpr (OTF) {
+                wxc = axis_coord(src.gs.start[0], src.gs.end[0], s.fine[0], valid ? gx : 0, src.gs.center[0]);
+                wyc = axis_coord(src.gs.start[1], src.gs.end[1], s.fine[1], valid ? gy : 0, src.gs.center[1]);
+                wzc = axis_coord(src.gs.start[2], src.gs.end[2], s.fine[2], valid ? gz : 0, src.gs.center[2]);
+            }
+            camera_sum<LPV, false, OTF, CASC, 1, JPL, (MODE >= 2 && MODE <= 4) ? MODE : 0, true>(
+                acc, valid, gn, wxc, wyc, wzc, grs, lcam, rt, src.im, frame_cl, img, pix_bytes, qo, q, V, GV, W, H, sxs,
+                sys);
+        }
         float o[JPL];
         unsigned ou[JPL];
 #pragma unroll
         for (int k = 0; k < JPL; ++k) {
             // clamp(0,1) of the mean; +0.0f turns a -0 into +0 (unsigned max order below)
-            o[k] = valid ? clampf(acc[k] / fV, 0.0f, 1.0f) + 0.0f : 0.0f;
+            o[k] = valid ? clampf(acc[0][k] / fV, 0.0f, 1.0f) + 0.0f : 0.0f;
             ou[k] = zok ? __builtin_bit_cast(unsigned, o[k]) : 0u;  // beyond the cube: neutral
         }
         if constexpr (MODE == 1 || MODE == 4) {  // probe: keep the sums live, no planes
-            if (offset && zok && (acc[0] + acc[1] + acc[2] + acc[3]) == -1.0f) offset[(size_t)p * 3] = o[0];
+            if (offset && zok && (acc[0][0] + acc[0][1] + acc[0][2] + acc[0][3]) == -1.0f) offset[(size_t)p * 3] = o[0];
             continue;
         }
         if (cubes && zok) {
@@ -450,22 +342,22 @@ __device__ __forceinline__ void person_cl_body(const float *__restrict__ cl,
 
 template <int LPV, bool OTF, bool CASC, int MODE = 0>
 __global__ __launch_bounds__(64 * LPV) void person_cl_kernel(const float *__restrict__ cl,
-                                                             const float *__restrict__ fgrid, PersonCoords pc,
+                                                             const float *__restrict__ fgrid, CoordSource src,
                                                              const float *__restrict__ props,
                                                              const int32_t *__restrict__ frame_of, fvp_person_spec s,
                                                              float *__restrict__ cubes, float *__restrict__ planes,
                                                              float *__restrict__ offset, int P, int V, int J, int Jst,
                                                              int H, int W, int xmap, int xsplit, int zsplit,
                                                              unsigned pix_bytes, int xy_direct) {
-    person_cl_body<LPV, OTF, CASC, MODE, 4>(cl, fgrid, pc, props, frame_of, s, cubes, planes, offset, P, V, J, Jst, H, W,
-                                            xmap, xsplit, zsplit, pix_bytes, xy_direct);
+    person_cl_body<LPV, OTF, CASC, MODE, 4>(cl, fgrid, src, props, frame_of, s, cubes, planes, offset, P, V, J, Jst, H,
+                                            W, xmap, xsplit, zsplit, pix_bytes, xy_direct);
 }
 
 // The same on fp16 channels-last pixels read in place (cached fine grid): 8 joints
 // per lane, blocks of 64 z x LPV threads with LPV = 1 / 2 / 4 for J <= 8 / 16 / 32.
 template <int LPV, bool CASC>
 __global__ __launch_bounds__(64 * LPV) void person_cl_h8_kernel(const float *__restrict__ cl,
-                                                                const float *__restrict__ fgrid, PersonCoords pc,
+                                                                const float *__restrict__ fgrid, CoordSource src,
                                                                 const float *__restrict__ props,
                                                                 const int32_t *__restrict__ frame_of,
                                                                 fvp_person_spec s, float *__restrict__ cubes,
@@ -473,8 +365,8 @@ __global__ __launch_bounds__(64 * LPV) void person_cl_h8_kernel(const float *__r
                                                                 int P, int V, int J, int Jst, int H, int W, int xmap,
                                                                 int xsplit, int zsplit, unsigned pix_bytes,
                                                                 int xy_direct) {
-    person_cl_body<LPV, false, CASC, 0, 8>(cl, fgrid, pc, props, frame_of, s, cubes, planes, offset, P, V, J, Jst, H, W,
-                                           xmap, xsplit, zsplit, pix_bytes, xy_direct);
+    person_cl_body<LPV, false, CASC, 0, 8>(cl, fgrid, src, props, frame_of, s, cubes, planes, offset, P, V, J, Jst, H,
+                                           W, xmap, xsplit, zsplit, pix_bytes, xy_direct);
 }
 
 // Small launches (per-frame calls) split each row's x walk over 2-4 blocks.
@@ -561,7 +453,7 @@ static int person_plan(bool otf, int cp, bool cl_half, bool hm_aligned, int B, i
 }
 
 template <int LPV, bool OTF, bool CASC, int JPL = 4>
-static void launch_person_cl(const float *cl, const float *fgrid, const PersonCoords &pc, const float *props,
+static void launch_person_cl(const float *cl, const CoordSource &src, const float *props,
                              const int32_t *frame_of, const fvp_person_spec &s, float *cubes, float *planes,
                              float *offset, int P, int V, int J, int Jst, int H, int W, unsigned pix_bytes,
                              const PersonPlan &pl, hipStream_t st) {
@@ -578,10 +470,11 @@ static void launch_person_cl(const float *cl, const float *fgrid, const PersonCo
     const int xmap = 1, xsplit = pl.xsplit, zsplit = pl.zsplit, xy_direct = pl.xy_direct;
     const dim3 grid(pl.blocks);
     if constexpr (JPL == 8)
-        hipLaunchKernelGGL((person_cl_h8_kernel<LPV, CASC>), grid, dim3(64 * LPV), 0, st, cl, fgrid, pc, props, frame_of,
-                           s, cubes, planes, offset, P, V, J, Jst, H, W, xmap, xsplit, zsplit, pix_bytes, xy_direct);
+        hipLaunchKernelGGL((person_cl_h8_kernel<LPV, CASC>), grid, dim3(64 * LPV), 0, st, cl, src.grids, src, props,
+                           frame_of, s, cubes, planes, offset, P, V, J, Jst, H, W, xmap, xsplit, zsplit, pix_bytes,
+                           xy_direct);
     else
-        hipLaunchKernelGGL((person_cl_kernel<LPV, OTF, CASC>), grid, dim3(64 * LPV), 0, st, cl, fgrid, pc, props,
+        hipLaunchKernelGGL((person_cl_kernel<LPV, OTF, CASC>), grid, dim3(64 * LPV), 0, st, cl, src.grids, src, props,
                            frame_of, s, cubes, planes, offset, P, V, J, Jst, H, W, xmap, xsplit, zsplit, pix_bytes,
                            xy_direct);
 }
@@ -610,17 +503,16 @@ extern "C" size_t fvp_person_workspace_bytes(int B, int V, int J, int H, int W) 
 
 namespace fvp {
 
-static int person_planes_any(const float *heatmaps, int cp, int B, int V, int J, int H, int W,
-                             const float *fine_grid, const PersonCoords *pc, const fvp_person_spec *spec,
-                             const float *proposals, const int32_t *frame_of, int P, float *cubes, float *planes,
-                             float *offset, void *workspace, size_t workspace_bytes, void *stream,
-                             bool cl_half = false) {
-    if (!heatmaps || !spec || (!fine_grid && !pc)) return FVP_ERR_NULL;
+static int person_planes_any(const float *heatmaps, int cp, int B, int V, int J, int H, int W, const CoordSource &src,
+                             const fvp_person_spec *spec, const float *proposals, const int32_t *frame_of, int P,
+                             float *cubes, float *planes, float *offset, void *workspace, size_t workspace_bytes,
+                             void *stream, bool cl_half = false) {
+    if (!heatmaps || !spec || (!src.grids && !src.cams)) return FVP_ERR_NULL;
     if (P <= 0) return FVP_OK;
     if (!proposals) return FVP_ERR_NULL;
     PersonPlan pl;
-    const int sc = person_plan(pc != nullptr, cp, cl_half, ((unsigned long long)heatmaps & 15ull) == 0, B, V, J, H, W,
-                               spec->bins, spec->fine, P, planes != nullptr, pl);
+    const int sc = person_plan(src.cams != nullptr, cp, cl_half, ((unsigned long long)heatmaps & 15ull) == 0, B, V, J,
+                               H, W, spec->bins, spec->fine, P, planes != nullptr, pl);
     if (sc != FVP_OK) return sc;
     if (pl.layout) {
         const size_t need = (size_t)B * cl_frame_bytes(V, pl.s[0].Jc, H, W);
@@ -633,56 +525,40 @@ static int person_planes_any(const float *heatmaps, int cp, int B, int V, int J,
         const hipError_t e = hipMemsetAsync(planes, 0, n * 4, st);
         if (e != hipSuccess) return (int)e;
     }
-    const PersonCoords none{};
-    const PersonCoords &c = pc ? *pc : none;
     const size_t HW = (size_t)H * W, S2 = (size_t)SX * SY, S3 = S2 * SZ;
+    using TT = std::true_type;
+    using FF = std::false_type;
     for (int k = 0; k < pl.n; ++k) {
         const int j0 = pl.s[k].j0, Jc = pl.s[k].Jc;
-        const unsigned pix_bytes = pl.s[k].pix_bytes;
         float *cb = cubes ? cubes + j0 * S3 : nullptr;
         float *pp = planes ? planes + j0 * S2 : nullptr;
-        if (cl_half) {
-            const float *clh = reinterpret_cast<const float *>(reinterpret_cast<const _Float16 *>(heatmaps) + j0);
-            auto go = [&](auto lpv) {
-                constexpr int L = decltype(lpv)::value;
-                if (pl.casc)
-                    launch_person_cl<L, false, true, 8>(clh, fine_grid, c, proposals, frame_of, *spec, cb, pp, offset, P,
-                                                        V, Jc, J, H, W, pix_bytes, pl, st);
-                else
-                    launch_person_cl<L, false, false, 8>(clh, fine_grid, c, proposals, frame_of, *spec, cb, pp, offset,
-                                                         P, V, Jc, J, H, W, pix_bytes, pl, st);
-            };
-            switch (pl.s[k].lpv) {
-                case 1: go(std::integral_constant<int, 1>{}); break;
-                case 2: go(std::integral_constant<int, 2>{}); break;
-                default: go(std::integral_constant<int, 4>{}); break;
-            }
-            continue;
-        }
-        const float *cl = cp ? heatmaps + j0 : reinterpret_cast<const float *>(workspace);
-#define FVP_PERSON_CASE(L)                                                                                            \
-    if (pl.layout)                                                                                                    \
-        launch_layout<L, float>(heatmaps + j0 * HW, B, V, Jc, J, H, W, reinterpret_cast<float *>(workspace), st);      \
-    if (pl.otf && pl.casc)                                                                                            \
-        launch_person_cl<L, true, true>(cl, nullptr, c, proposals, frame_of, *spec, cb, pp, offset, P, V, Jc, J, H,   \
-                                        W, pix_bytes, pl, st);                                                        \
-    else if (pl.otf)                                                                                                  \
-        launch_person_cl<L, true, false>(cl, nullptr, c, proposals, frame_of, *spec, cb, pp, offset, P, V, Jc, J, H,  \
-                                         W, pix_bytes, pl, st);                                                       \
-    else if (pl.casc)                                                                                                 \
-        launch_person_cl<L, false, true>(cl, fine_grid, c, proposals, frame_of, *spec, cb, pp, offset, P, V, Jc, J,   \
-                                         H, W, pix_bytes, pl, st);                                                    \
-    else                                                                                                              \
-        launch_person_cl<L, false, false>(cl, fine_grid, c, proposals, frame_of, *spec, cb, pp, offset, P, V, Jc, J,  \
-                                          H, W, pix_bytes, pl, st);                                                   \
-    break;
-        switch (pl.s[k].lpv) {
-            case 1: FVP_PERSON_CASE(1)
-            case 2: FVP_PERSON_CASE(2)
-            case 4: FVP_PERSON_CASE(4)
-            default: FVP_PERSON_CASE(8)
-        }
-#undef FVP_PERSON_CASE
+        // the slice's pixels: fp16 / fp32 channels-last in place from channel j0 on, or the workspace
+        const float *cl = cl_half ? reinterpret_cast<const float *>(reinterpret_cast<const _Float16 *>(heatmaps) + j0)
+                          : cp    ? heatmaps + j0
+                                  : reinterpret_cast<const float *>(workspace);
+        auto go = [&](auto lpv, auto otf, auto casc, auto jpl) {
+            constexpr int L = decltype(lpv)::value, JPL = decltype(jpl)::value;
+            if constexpr (JPL == 4)
+                if (pl.layout)
+                    launch_layout<L, float>(heatmaps + j0 * HW, B, V, Jc, J, H, W,
+                                            reinterpret_cast<float *>(workspace), st);
+            launch_person_cl<L, decltype(otf)::value, decltype(casc)::value, JPL>(
+                cl, src, proposals, frame_of, *spec, cb, pp, offset, P, V, Jc, J, H, W, pl.s[k].pix_bytes, pl, st);
+        };
+        auto flags = [&](auto lpv, auto jpl) {  // (fp16 pixels: cached fine grid only, person_plan)
+            if constexpr (decltype(jpl)::value == 4)
+                if (pl.otf) return pl.casc ? go(lpv, TT{}, TT{}, jpl) : go(lpv, TT{}, FF{}, jpl);
+            return pl.casc ? go(lpv, FF{}, TT{}, jpl) : go(lpv, FF{}, FF{}, jpl);
+        };
+        auto lanes = [&](auto jpl) {  // (8 lanes per voxel: fp32 pixels only, lanes_per_voxel_h)
+            const int lpv = pl.s[k].lpv;
+            if (lpv == 1) return flags(std::integral_constant<int, 1>{}, jpl);
+            if (lpv == 2) return flags(std::integral_constant<int, 2>{}, jpl);
+            if constexpr (decltype(jpl)::value == 4)
+                if (lpv == 8) return flags(std::integral_constant<int, 8>{}, jpl);
+            return flags(std::integral_constant<int, 4>{}, jpl);
+        };
+        cl_half ? lanes(std::integral_constant<int, 8>{}) : lanes(std::integral_constant<int, 4>{});
     }
     return (int)hipGetLastError();
 }
@@ -725,7 +601,7 @@ extern "C" int fvp_person_planes(const float *heatmaps, int B, int V, int J, int
                                  float *cubes, float *planes, float *offset, void *workspace, size_t workspace_bytes,
                                  void *stream) {
     if (!fine_grid) return FVP_ERR_NULL;
-    return fvp::person_planes_any(heatmaps, 0, B, V, J, H, W, fine_grid, nullptr, spec, proposals, frame_of, P,
+    return fvp::person_planes_any(heatmaps, 0, B, V, J, H, W, fvp::CoordSource{fine_grid}, spec, proposals, frame_of, P,
                                   cubes, planes, offset, workspace, workspace_bytes, stream);
 }
 
@@ -738,9 +614,9 @@ extern "C" int fvp_person_planes_cams(const float *heatmaps, int B, int V, int J
     if (img->hm_w != W || img->hm_h != H) return FVP_ERR_SHAPE;
     for (int a = 0; a < 3; ++a)
         if (fine_grid_spec->bins[a] != spec->fine[a]) return FVP_ERR_SHAPE;
-    const fvp::PersonCoords pc{cams, resize_t, *fine_grid_spec, fvp::image_consts(*img)};
-    return fvp::person_planes_any(heatmaps, 0, B, V, J, H, W, nullptr, &pc, spec, proposals, frame_of, P, cubes,
-                                  planes, offset, workspace, workspace_bytes, stream);
+    const fvp::CoordSource src{nullptr, cams, resize_t, *fine_grid_spec, fvp::image_consts(*img), 0};
+    return fvp::person_planes_any(heatmaps, 0, B, V, J, H, W, src, spec, proposals, frame_of, P, cubes, planes, offset,
+                                  workspace, workspace_bytes, stream);
 }
 
 extern "C" int fvp_person_planes_cl(const float *heatmaps_cl, int cp, int B, int V, int J, int H, int W,
@@ -749,8 +625,8 @@ extern "C" int fvp_person_planes_cl(const float *heatmaps_cl, int cp, int B, int
                                     void *stream) {
     if (!fine_grid) return FVP_ERR_NULL;
     if (const int sc = fvp::person_entry_check(true, false, cp, J, true)) return sc;
-    return fvp::person_planes_any(heatmaps_cl, cp, B, V, J, H, W, fine_grid, nullptr, spec, proposals, frame_of, P,
-                                  cubes, planes, offset, nullptr, 0, stream);
+    return fvp::person_planes_any(heatmaps_cl, cp, B, V, J, H, W, fvp::CoordSource{fine_grid}, spec, proposals,
+                                  frame_of, P, cubes, planes, offset, nullptr, 0, stream);
 }
 
 extern "C" int fvp_person_planes_cl_f16(const void *heatmaps_cl, int cp, int B, int V, int J, int H, int W,
@@ -760,6 +636,7 @@ extern "C" int fvp_person_planes_cl_f16(const void *heatmaps_cl, int cp, int B, 
     if (!heatmaps_cl || !fine_grid || !spec) return FVP_ERR_NULL;
     if (const int sc = fvp::person_entry_check(false, true, cp, J, ((unsigned long long)heatmaps_cl & 15ull) == 0))
         return sc;
-    return fvp::person_planes_any(reinterpret_cast<const float *>(heatmaps_cl), cp, B, V, J, H, W, fine_grid, nullptr,
-                                  spec, proposals, frame_of, P, cubes, planes, offset, nullptr, 0, stream, true);
+    return fvp::person_planes_any(reinterpret_cast<const float *>(heatmaps_cl), cp, B, V, J, H, W,
+                                  fvp::CoordSource{fine_grid}, spec, proposals, frame_of, P, cubes, planes, offset,
+                                  nullptr, 0, stream, true);
 }

@@ -44,19 +44,6 @@
 namespace fvp {
 
 // -- gather pass ----------------------------------------------------------------
-// Where the sampling coordinates come from: a packed per-sequence grid
-// (OTF = false), or the camera records, projected on the fly with the exact
-// fp32 sequence of project_grid_kernel (OTF = true; used when the grid would
-// not stay cache-resident, e.g. 31 cameras x 160x160x64 = 420 MB).
-struct CoordSource {
-    const float *grids;     // packed grids [S][N][GV][2]            (!OTF)
-    const float *cams;      // camera records [S][V][FVP_CAM_STRIDE] (OTF)
-    const float *resize_t;  // [2][3]                                (OTF)
-    fvp_grid_spec gs;       // (OTF) the whole grid: x-row i of a launch is row x_off + i of gs
-    ImageConsts im;
-    int x_off;              // (OTF) first x-row of an x-slab launch (0: the whole grid)
-};
-
 // Whether a block of T voxels takes the vector epilogue (store_stage; the host
 // reports the same predicate per launch through fvp_voxelize_plan).
 __host__ __device__ __forceinline__ bool stage_vec(int T, int SP, int Z, long long N, bool cube16) {
@@ -116,9 +103,8 @@ __device__ __forceinline__ void store_stage(const float *__restrict__ stage, int
     }
 }
 
-// JPL joints per lane: 4 (a lane's 16 B = 4 fp32 joints, or the pair table's 2 x 4
-// fp16) or 8 (fp16 channels-last pixels read in place: 16 B = 8 fp16 joints, so a
-// voxel needs half the lanes and a wave's four tap loads serve twice the voxels).
+// A gather block: its columns, passes of 256/LPV voxels (camera_sum, fvp_layout.h, each)
+// into the stage, then store_stage.  JPL joints per lane: 4 or 8 (camera_sum).
 template <int LPV, bool PAIR, bool OTF, bool CASC, int NF, int JPL = 4>
 __device__ __forceinline__ void voxelize_body(const void *__restrict__ tab, const CoordSource &src_,
                                                        const int32_t *__restrict__ grid_index, int frame0,
@@ -126,15 +112,12 @@ __device__ __forceinline__ void voxelize_body(const void *__restrict__ tab, cons
                                                        int Jst, int H, int W, int X, int Y, int Z, int cols,
                                                        int col_blocks, int SP, int band, unsigned pixb,
                                                        bool cube16) {
-    static_assert(!PAIR || LPV == 4, "the fp16 pair table has 4 lanes per voxel");
-    static_assert(JPL == 4 || (JPL == 8 && !PAIR && NF == 1), "fp16 channels-last: one frame per pixel, no table");
     constexpr int JP = JPL * LPV;
     // 8 joints per lane with the 16-camera cascade under the cached-grid kernel's
     // 64 VGPRs: the completed blocks' sums wait in the voxel's own stage slots (LDS,
     // written again only by this lane, at the end) instead of 8 more registers
     constexpr bool PARK = JPL == 8 && CASC && !OTF;
     constexpr int VPP = 256 / LPV;  // voxels per pass
-    constexpr int CPG = 2 * LPV;    // cameras per grid load (2 per lane)
     extern __shared__ __attribute__((aligned(16))) float stage[];  // [NF][JP][SP] (+ OTF camera records)
     const int L = xcd_remap(blockIdx.x, gridDim.x);
     const int bl = L / col_blocks;   // frame group within the chunk (NF frames share each table entry)
@@ -177,8 +160,7 @@ __device__ __forceinline__ void voxelize_body(const void *__restrict__ tab, cons
     // per-camera image of this frame group in the workspace: each pixel / pair
     // entry holds the NF frames' copies back to back (one 128-B line at NF = 2)
     const unsigned pix = PAIR ? 64u : pixb;  // bytes of one frame's pixel (>= JP*4) / pair entry
-    const unsigned unit = pix * NF;             // bytes per entry
-    const unsigned img = (PAIR ? (unsigned)(H * (W + 1)) : (unsigned)(H * W)) * unit;  // bytes per camera
+    const unsigned img = (PAIR ? (unsigned)(H * (W + 1)) : (unsigned)(H * W)) * pix * NF;  // bytes per camera
     const char *__restrict__ frame_tab = (const char *)tab + (size_t)bl * V * img;
 
     for (int i0 = 0; i0 < T; i0 += VPP) {
@@ -191,11 +173,6 @@ __device__ __forceinline__ void voxelize_body(const void *__restrict__ tab, cons
         const int zl = sl / ncols, cl = sl - zl * ncols;
         const int ii = cl * Z + zl;
         const long long gn = (long long)(c0 + cl) * Z + zl;
-        float acc[NF][JPL], blk[NF][JPL];  // blk (CASC): completed 16-camera blocks (view_sum order)
-#pragma unroll
-        for (int f = 0; f < NF; ++f)
-#pragma unroll
-            for (int m = 0; m < JPL; ++m) acc[f][m] = blk[f][m] = 0.0f;
         float wx_ = 0.f, wy_ = 0.f, wz_ = 0.f;  // OTF: voxel centre (compute_grid, project_whole.py:43-79)
         if constexpr (OTF) {
             const int iz = zl;
@@ -205,138 +182,29 @@ __device__ __forceinline__ void voxelize_body(const void *__restrict__ tab, cons
             wy_ = axis_coord(src_.gs.start[1], src_.gs.end[1], Y, (int)(r % Y), src_.gs.center[1]);
             wz_ = axis_coord(src_.gs.start[2], src_.gs.end[2], Z, iz, src_.gs.center[2]);
         }
-        for (int v0 = 0; v0 < V; v0 += CPG) {
-            if constexpr (PARK) {
-                // a block of 16 cameras is complete (CPG divides 16, so only ever at a
-                // group's first camera): fold it into the parked sum, before this
-                // group's taps are set up (fewest live registers)
-                if ((v0 & 15) == 0 && v0 > 0) {
-                    if (valid) {
-                        // (the slot addresses are formed here, behind an opaque copy, or the
-                        // compiler keeps all 8 of them in registers across the camera loop)
-                        int slot = JPL * q * SP + ii;
-                        asm volatile("" : "+v"(slot));
-#pragma unroll
-                        for (int m = 0; m < JPL; ++m) {
-                            float *p = stage + slot + m * SP;
-                            *p = (v0 == 16 ? 0.0f : *p) + acc[0][m];
-                        }
-                    }
-#pragma unroll
-                    for (int m = 0; m < JPL; ++m) acc[0][m] = 0.0f;
-                }
-            }
-            // cameras v0+2q, v0+2q+1 of voxel n0+ii (past V: padding, unused)
-            float g[4];
-            if constexpr (OTF) {
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const Cam c = load_cam(lcam + min(v0 + 2 * q + h, GV - 1) * FVP_CAM_STRIDE);
-                    float px, py;
-                    project_point(c, wx_, wy_, wz_, px, py);
-                    pixel_to_sample(px, py, rt, src_.im, g[2 * h], g[2 * h + 1]);
-                }
-            } else {
-                // slots v0+2q, v0+2q+1 (past the row: the next voxel's or 0)
-                const u32x4 graw = __builtin_amdgcn_raw_buffer_load_b128(
-                    grs, (unsigned)((gn * GV + v0 + 2 * q) * 8), 0, 0);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) g[k] = __builtin_bit_cast(float, (unsigned)graw[k]);
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) g[k] = valid ? g[k] : -2.0f;
-            const Taps4<PAIR> t0 = setup_taps<PAIR>(g[0], g[1], sxs, sys, W, H, unit);
-            const Taps4<PAIR> t1 = setup_taps<PAIR>(g[2], g[3], sxs, sys, W, H, unit);
-            static_for(std::make_integer_sequence<int, CPG>{}, [&](auto kc) {
-                constexpr int k = decltype(kc)::value;
-                constexpr int S = k >> 1;  // lane of the group that set this camera up
-                const int v = v0 + k;
-                if (v >= V) return;
-                if constexpr (CASC && !PARK) {
-                    if ((v & 15) == 0 && v > 0) {  // a block of 16 cameras is complete: fold it (fvp_device.h)
-#pragma unroll
-                        for (int f = 0; f < NF; ++f)
+        float acc[NF][JPL];
+        if constexpr (PARK) {
+            // (the slot addresses are formed where they are used, behind an opaque copy, or
+            // the compiler keeps all 8 of them in registers across the camera loop)
+            camera_sum<LPV, PAIR, OTF, CASC, NF, JPL>(
+                acc, valid, gn, wx_, wy_, wz_, grs, lcam, rt, src_.im, frame_tab, img, pix, qo, q, V, GV, W, H, sxs,
+                sys, [&](int v0, float(&a)[NF][JPL]) {
+                    // a block of 16 cameras is complete: fold it into the parked sum, before this
+                    // group's taps are set up (fewest live registers)
+                    if ((v0 & 15) == 0 && v0 > 0) {
+                        if (valid) {
+                            int slot = JPL * q * SP + ii;
+                            asm volatile("" : "+v"(slot));
 #pragma unroll
                             for (int m = 0; m < JPL; ++m) {
-                                blk[f][m] = blk[f][m] + acc[f][m];
-                                acc[f][m] = 0.0f;
+                                float *p = stage + slot + m * SP;
+                                *p = (v0 == 16 ? 0.0f : *p) + a[0][m];
                             }
-                    }
-                }
-                const Taps4<PAIR> &src = (k & 1) ? t1 : t0;
-                unsigned o[Taps4<PAIR>::NO];
-                unsigned all = kOOB;
-#pragma unroll
-                for (int m = 0; m < Taps4<PAIR>::NO; ++m) {
-                    o[m] = group_bcast<LPV, S>(src.o[m]);
-                    all &= o[m];
-                }
-                // whole wave off-image (every tap's kOOB bit set): contributes exactly 0
-                if (!__builtin_amdgcn_ballot_w64((all & kOOB) == 0u)) return;
-                float w[4];
-#pragma unroll
-                for (int m = 0; m < 4; ++m) w[m] = group_bcast<LPV, S>(src.w[m]);
-                const __amdgpu_buffer_rsrc_t rs = uniform_rsrc(frame_tab + (size_t)v * img, img);
-                if constexpr (PAIR) {
-                    // r0 = [a j0 j1 | a j2 j3 | b j0 j1 | b j2 j3] (row y0), r1 likewise (c, d; row y1)
-                    u32x4 r0[NF], r1[NF];
-#pragma unroll
-                    for (int f = 0; f < NF; ++f) {
-                        r0[f] = __builtin_amdgcn_raw_buffer_load_b128(rs, o[0] + f * pix + qo, 0, 0);
-                        r1[f] = __builtin_amdgcn_raw_buffer_load_b128(rs, o[1] + f * pix + qo, 0, 0);
-                    }
-#pragma unroll
-                    for (int f = 0; f < NF; ++f)
-                        static_for(std::make_integer_sequence<int, 4>{}, [&](auto mc) {
-                            constexpr int m = decltype(mc)::value, HI = m & 1;
-                            const unsigned ua = r0[f][m >> 1], ub = r0[f][2 + (m >> 1)];
-                            const unsigned uc = r1[f][m >> 1], ud = r1[f][2 + (m >> 1)];
-                            // fd*w3 + (fc*w2 + (fb*w1 + fa*w0)), the fp16 taps converted inside the fmas
-                            const float t = fma_h<HI>(ua, w[0], -0.0f);
-                            acc[f][m] = acc[f][m] + fma_h<HI>(ud, w[3], fma_h<HI>(uc, w[2], fma_h<HI>(ub, w[1], t)));
-                        });
-                } else {
-                    u32x4 a[NF], bq[NF], c[NF], d[NF];
-#pragma unroll
-                    for (int f = 0; f < NF; ++f) {
-                        a[f] = __builtin_amdgcn_raw_buffer_load_b128(rs, o[0] + f * pix + qo, 0, 0);
-                        bq[f] = __builtin_amdgcn_raw_buffer_load_b128(rs, o[1] + f * pix + qo, 0, 0);
-                        c[f] = __builtin_amdgcn_raw_buffer_load_b128(rs, o[2] + f * pix + qo, 0, 0);
-                        d[f] = __builtin_amdgcn_raw_buffer_load_b128(rs, o[3] + f * pix + qo, 0, 0);
-                    }
-                    if constexpr (JPL == 8) {
-                        // word i of a pixel piece = joints 8q+2i (low half), 8q+2i+1 (high half):
-                        // fd*w3 + (fc*w2 + (fb*w1 + fa*w0)), the fp16 taps converted inside the fmas
-                        static_for(std::make_integer_sequence<int, 8>{}, [&](auto mc) {
-                            constexpr int m = decltype(mc)::value, HI = m & 1, wd = m >> 1;
-                            const float t = fma_h<HI>(a[0][wd], w[0], -0.0f);
-                            acc[0][m] = acc[0][m] + fma_h<HI>(d[0][wd], w[3],
-                                                              fma_h<HI>(c[0][wd], w[2], fma_h<HI>(bq[0][wd], w[1], t)));
-                        });
-                    } else {
-#pragma unroll
-                    for (int f = 0; f < NF; ++f)
-#pragma unroll
-                        for (int m = 0; m < 4; ++m) {
-                            const float fa = __builtin_bit_cast(float, (unsigned)a[f][m]);
-                            const float fb = __builtin_bit_cast(float, (unsigned)bq[f][m]);
-                            const float fc = __builtin_bit_cast(float, (unsigned)c[f][m]);
-                            const float fd = __builtin_bit_cast(float, (unsigned)d[f][m]);
-                            acc[f][m] = acc[f][m] + __builtin_fmaf(fd, w[3], __builtin_fmaf(fc, w[2],
-                                                                   __builtin_fmaf(fb, w[1], fa * w[0])));
                         }
+#pragma unroll
+                        for (int m = 0; m < JPL; ++m) a[0][m] = 0.0f;
                     }
-                }
-            });
-        }
-        // the sum's final levels (fvp_device.h): remainder + blocks, or + 0 (a -0 sum becomes +0)
-#pragma unroll
-        for (int f = 0; f < NF; ++f)
-#pragma unroll
-            for (int m = 0; m < JPL; ++m) {
-                if constexpr (!PARK) acc[f][m] = acc[f][m] + (CASC ? blk[f][m] : 0.0f);
-            }
-        if constexpr (PARK) {
+                });
             int slot = JPL * q * SP + ii;
             asm volatile("" : "+v"(slot));
             if (valid) {
@@ -346,12 +214,16 @@ __device__ __forceinline__ void voxelize_body(const void *__restrict__ tab, cons
                     *p = clampf((acc[0][m] + *p) / fV, 0.0f, 1.0f);
                 }
             }
-        } else if (valid) {
+        } else {
+            camera_sum<LPV, PAIR, OTF, CASC, NF, JPL>(acc, valid, gn, wx_, wy_, wz_, grs, lcam, rt, src_.im, frame_tab,
+                                                      img, pix, qo, q, V, GV, W, H, sxs, sys);
+            if (valid) {
 #pragma unroll
-            for (int f = 0; f < NF; ++f)
+                for (int f = 0; f < NF; ++f)
 #pragma unroll
-                for (int m = 0; m < JPL; ++m)
-                    stage[(f * JP + JPL * q + m) * SP + ii] = clampf(acc[f][m] / fV, 0.0f, 1.0f);
+                    for (int m = 0; m < JPL; ++m)
+                        stage[(f * JP + JPL * q + m) * SP + ii] = clampf(acc[f][m] / fV, 0.0f, 1.0f);
+            }
         }
     }
     __syncthreads();
@@ -601,6 +473,16 @@ struct VoxJob {
     PlanSink *plan;  // fvp_voxelize_plan: record the launches instead of making them
 };
 
+// The launch shape of frames [f0, f0 + frames); one that gather_cfg refuses goes into
+// the plan with its status (the call ends there).
+template <int LPV, bool PAIR, bool OTF, bool CASC, int NF, int JPL>
+static int job_cfg(const VoxJob &j, int f0, int frames, GatherCfg &c) {
+    const int st = gather_cfg<LPV, OTF, JPL>(frames, NF, j.V, j.X, j.Y, j.Z, c);
+    if (st != FVP_OK && j.plan)
+        plan_record<LPV, PAIR, OTF, CASC, NF, JPL>(*j.plan, f0, frames, c, j.J, j.X, j.Y, j.Z, j.cube, 0, st);
+    return st;
+}
+
 // Frames [first, last) of the batch (a multiple of NF of them), chunk by chunk:
 // layout pass into the workspace, then the gather, NF frames per table entry.
 template <int LPV, bool PAIR, bool OTF, bool CASC, int NF, typename T>
@@ -610,12 +492,7 @@ static int run_chunks(const T *hm, int first, int last, const VoxJob &j, const C
     const int B = last - first;
     const int chunk = max(NF, chunk_frames(B, j.V, j.J, j.H, j.W, half) / NF * NF);
     GatherCfg c;
-    if (gather_cfg<LPV, OTF>(min(chunk, B), NF, j.V, j.X, j.Y, j.Z, c) != FVP_OK) {
-        if (j.plan)
-            plan_record<LPV, PAIR, OTF, CASC, NF, 4>(*j.plan, first, min(chunk, B), c, j.J, j.X, j.Y, j.Z, j.cube, 0,
-                                                     FVP_ERR_SHAPE);
-        return FVP_ERR_SHAPE;
-    }
+    if (const int st = job_cfg<LPV, PAIR, OTF, CASC, NF, 4>(j, first, min(chunk, B), c)) return st;
     const size_t frame_elems = (size_t)j.V * j.Jst * j.H * j.W;
     for (int f0 = first; f0 < last; f0 += chunk) {
         const int nb = min(chunk, last - f0);
@@ -636,56 +513,30 @@ static int run_chunks(const T *hm, int first, int last, const VoxJob &j, const C
     return j.plan ? FVP_OK : (int)hipGetLastError();
 }
 
-// Heatmaps already channels-last ([B][V][H][W][cp] fp32, the slice's joints
-// from hm_cl on, e.g. the PoseResNet backbone's NHWC output): the gather reads
-// them in place, one launch for the whole batch, no layout pass, no workspace.
-template <bool OTF, bool CASC>
-static int run_direct(const float *hm_cl, int cp, int B, const VoxJob &j, const CoordSource &src, hipStream_t s) {
-    const unsigned pixb = (unsigned)cp * 4u;
+// Heatmaps already channels-last ([B][V][H][W][cp], the slice's joints from
+// hm_cl on, e.g. the PoseResNet backbone's NHWC output): the gather reads them
+// in place, one launch for the whole batch, no layout pass, no workspace.
+// fp16 pixels (T = _Float16): a pixel of 16 joints is 32 B, a lane's 16-B load
+// carries 8 joints, so a voxel takes 1 / 2 / 4 lanes for J <= 8 / 16 / 32 and a
+// wave's four tap loads cover twice the voxels.
+template <bool OTF, bool CASC, typename T>
+static int run_direct(const T *hm_cl, int cp, int B, const VoxJob &j, const CoordSource &src, hipStream_t s) {
+    constexpr int JPL = sizeof(T) == 2 ? 8 : 4;
+    const unsigned pixb = (unsigned)cp * (unsigned)sizeof(T);
     auto go = [&](auto lpv) -> int {
         constexpr int LPV = decltype(lpv)::value;
         GatherCfg c;
-        if (gather_cfg<LPV, OTF>(B, 1, j.V, j.X, j.Y, j.Z, c) != FVP_OK) {
-            if (j.plan)
-                plan_record<LPV, false, OTF, CASC, 1, 4>(*j.plan, 0, B, c, j.J, j.X, j.Y, j.Z, j.cube, 0, FVP_ERR_SHAPE);
-            return FVP_ERR_SHAPE;
-        }
-        launch_gather<LPV, false, OTF, CASC, 1>(hm_cl, 0, B, c, src, j.grid_index, j.V, j.J, j.Jst, j.H, j.W, j.X,
-                                               j.Y, j.Z, j.cube, j.xy, pixb, s, j.plan, 0);
+        if (const int st = job_cfg<LPV, false, OTF, CASC, 1, JPL>(j, 0, B, c)) return st;
+        launch_gather<LPV, false, OTF, CASC, 1, JPL>(hm_cl, 0, B, c, src, j.grid_index, j.V, j.J, j.Jst, j.H, j.W, j.X,
+                                                    j.Y, j.Z, j.cube, j.xy, pixb, s, j.plan, 0);
         return j.plan ? FVP_OK : (int)hipGetLastError();
     };
-    switch (lanes_per_voxel(j.J)) {
-        case 1: return go(std::integral_constant<int, 1>{});
-        case 2: return go(std::integral_constant<int, 2>{});
-        case 4: return go(std::integral_constant<int, 4>{});
-        default: return go(std::integral_constant<int, 8>{});
-    }
-}
-
-// The same for fp16 channels-last heatmaps ([B][V][H][W][cp] fp16): a pixel of
-// 16 joints is 32 B, a lane's 16-B load carries 8 joints, so a voxel takes 1 / 2 /
-// 4 lanes for J <= 8 / 16 / 32 and a wave's four tap loads cover twice the voxels.
-template <bool OTF, bool CASC>
-static int run_direct_h(const _Float16 *hm_cl, int cp, int B, const VoxJob &j, const CoordSource &src,
-                        hipStream_t s) {
-    const unsigned pixb = (unsigned)cp * 2u;
-    auto go = [&](auto lpv) -> int {
-        constexpr int LPV = decltype(lpv)::value;
-        GatherCfg c;
-        if (gather_cfg<LPV, OTF, 8>(B, 1, j.V, j.X, j.Y, j.Z, c) != FVP_OK) {
-            if (j.plan)
-                plan_record<LPV, false, OTF, CASC, 1, 8>(*j.plan, 0, B, c, j.J, j.X, j.Y, j.Z, j.cube, 0, FVP_ERR_SHAPE);
-            return FVP_ERR_SHAPE;
-        }
-        launch_gather<LPV, false, OTF, CASC, 1, 8>(hm_cl, 0, B, c, src, j.grid_index, j.V, j.J, j.Jst, j.H, j.W, j.X,
-                                                  j.Y, j.Z, j.cube, j.xy, pixb, s, j.plan, 0);
-        return j.plan ? FVP_OK : (int)hipGetLastError();
-    };
-    switch (lanes_per_voxel_h(j.J)) {
-        case 1: return go(std::integral_constant<int, 1>{});
-        case 2: return go(std::integral_constant<int, 2>{});
-        default: return go(std::integral_constant<int, 4>{});
-    }
+    const int lpv = JPL == 8 ? lanes_per_voxel_h(j.J) : lanes_per_voxel(j.J);
+    if (lpv == 1) return go(std::integral_constant<int, 1>{});
+    if (lpv == 2) return go(std::integral_constant<int, 2>{});
+    if constexpr (JPL == 4)  // (8 joints a lane: at most 4 lanes, lanes_per_voxel_h)
+        if (lpv == 8) return go(std::integral_constant<int, 8>{});
+    return go(std::integral_constant<int, 4>{});
 }
 
 // Frames per table entry: the fp16 pair table interleaves two frames per
@@ -735,26 +586,35 @@ static int slice_joints(int J) { return J < kJointSlice ? J : kJointSlice; }
 
 static size_t workspace_bytes(int B, int V, int J, int H, int W, bool half);
 
+// One call's joint slices: each slice's VoxJob (the cube / xy pointers start at the
+// slice) goes to run(job, j0, casc), casc = std::bool_constant of the 16-camera
+// cascade (V > 16); the first status other than FVP_OK ends the call.
+template <typename F>
+static int walk_slices(int V, int J, int H, int W, const int32_t *grid_index, int X, int Y, int Z, float *cube,
+                       float *xy, PlanSink *plan, F &&run) {
+    const size_t N = (size_t)X * Y * Z, XY = (size_t)X * Y;
+    for (int j0 = 0; j0 < J; j0 += kJointSlice) {
+        const VoxJob job{V, min(kJointSlice, J - j0), J, H, W, X, Y, Z, grid_index, cube ? cube + j0 * N : nullptr,
+                         xy ? xy + j0 * XY : nullptr, plan};
+        if (plan) plan->j0 = j0;
+        const int st = V > 16 ? run(job, j0, std::true_type{}) : run(job, j0, std::false_type{});
+        if (st != FVP_OK) return st;
+    }
+    return FVP_OK;
+}
+
 template <bool OTF, typename T>
 static int voxelize_any(const T *hm, int B, int V, int J, int H, int W, const CoordSource &src,
                         const int32_t *grid_index, int X, int Y, int Z, float *cube, float *xy, void *ws,
                         size_t ws_bytes, hipStream_t s, PlanSink *plan = nullptr) {
     const bool half = sizeof(T) == 2;
-    const int J1 = slice_joints(J);
     const size_t need = workspace_bytes(B, V, J, H, W, half);
     if (!ws || ws_bytes < need) return FVP_ERR_WORKSPACE;
-    if (frame_bytes(1, J1, H, W, half) > 0x7fffffffull) return FVP_ERR_SHAPE;  // 32-bit tap offsets
-    const size_t N = (size_t)X * Y * Z, XY = (size_t)X * Y, HW = (size_t)H * W;
-    for (int j0 = 0; j0 < J; j0 += kJointSlice) {
-        const VoxJob job{V, min(kJointSlice, J - j0), J, H, W, X, Y, Z, grid_index, cube ? cube + j0 * N : nullptr,
-                         xy ? xy + j0 * XY : nullptr, plan};
-        if (plan) plan->j0 = j0;
-        const T *h = hm + j0 * HW;
-        const int st = V > 16 ? voxelize_lpv<OTF, true, T>(h, B, job, src, ws, s)
-                              : voxelize_lpv<OTF, false, T>(h, B, job, src, ws, s);
-        if (st != FVP_OK) return st;
-    }
-    return FVP_OK;
+    if (frame_bytes(1, slice_joints(J), H, W, half) > 0x7fffffffull) return FVP_ERR_SHAPE;  // 32-bit tap offsets
+    const size_t HW = (size_t)H * W;
+    return walk_slices(V, J, H, W, grid_index, X, Y, Z, cube, xy, plan, [&](const VoxJob &job, int j0, auto casc) {
+        return voxelize_lpv<OTF, decltype(casc)::value, T>(hm + j0 * HW, B, job, src, ws, s);
+    });
 }
 
 // Channels-last input: the slice's channels start at hm_cl + j0 (cp >= j0 + 4 * LPV(slice) for every slice).
@@ -765,16 +625,9 @@ static int voxelize_cl_any(const float *hm_cl, int cp, int B, int V, int J, int 
     const int jl = ((J - 1) / kJointSlice) * kJointSlice;  // first joint of the last slice
     if (cp % 4 || cp < jl + 4 * lanes_per_voxel(J - jl)) return FVP_ERR_SHAPE;
     if ((size_t)H * W * cp * 4 > 0x7fffffffull) return FVP_ERR_SHAPE;  // 32-bit tap offsets per camera image
-    const size_t N = (size_t)X * Y * Z, XY = (size_t)X * Y;
-    for (int j0 = 0; j0 < J; j0 += kJointSlice) {
-        const VoxJob job{V, min(kJointSlice, J - j0), J, H, W, X, Y, Z, grid_index, cube ? cube + j0 * N : nullptr,
-                         xy ? xy + j0 * XY : nullptr, plan};
-        if (plan) plan->j0 = j0;
-        const int st = V > 16 ? run_direct<OTF, true>(hm_cl + j0, cp, B, job, src, s)
-                              : run_direct<OTF, false>(hm_cl + j0, cp, B, job, src, s);
-        if (st != FVP_OK) return st;
-    }
-    return FVP_OK;
+    return walk_slices(V, J, H, W, grid_index, X, Y, Z, cube, xy, plan, [&](const VoxJob &job, int j0, auto casc) {
+        return run_direct<OTF, decltype(casc)::value>(hm_cl + j0, cp, B, job, src, s);
+    });
 }
 
 // fp16 channels-last input (cp in fp16 elements): a lane of the last slice may
@@ -792,18 +645,10 @@ template <bool OTF>
 static int voxelize_cl_half_any(const _Float16 *hm_cl, int cp, int B, int V, int J, int H, int W,
                                 const CoordSource &src, const int32_t *grid_index, int X, int Y, int Z, float *cube,
                                 float *xy, hipStream_t s, PlanSink *plan = nullptr) {
-    const int st0 = check_cl_half(hm_cl, cp, J, H, W);
-    if (st0 != FVP_OK) return st0;
-    const size_t N = (size_t)X * Y * Z, XY = (size_t)X * Y;
-    for (int j0 = 0; j0 < J; j0 += kJointSlice) {
-        const VoxJob job{V, min(kJointSlice, J - j0), J, H, W, X, Y, Z, grid_index, cube ? cube + j0 * N : nullptr,
-                         xy ? xy + j0 * XY : nullptr, plan};
-        if (plan) plan->j0 = j0;
-        const int st = V > 16 ? run_direct_h<OTF, true>(hm_cl + j0, cp, B, job, src, s)
-                              : run_direct_h<OTF, false>(hm_cl + j0, cp, B, job, src, s);
-        if (st != FVP_OK) return st;
-    }
-    return FVP_OK;
+    if (const int st = check_cl_half(hm_cl, cp, J, H, W)) return st;
+    return walk_slices(V, J, H, W, grid_index, X, Y, Z, cube, xy, plan, [&](const VoxJob &job, int j0, auto casc) {
+        return run_direct<OTF, decltype(casc)::value>(hm_cl + j0, cp, B, job, src, s);
+    });
 }
 
 static int check_args(const void *heatmaps, int B, int V, int J, int H, int W, const float *grids, int X, int Y, int Z) {
@@ -836,7 +681,7 @@ static size_t workspace_bytes(int B, int V, int J, int H, int W, bool half) {
 // columns[b,k,j,z] = cube[b,j,flat[b,k],z] (human_detection_net.py:199-200)
 // recomputed for the K winners only, so an HDN forward that needs the cube
 // just for these columns can skip writing it (7.7 MB per C2 frame): the same
-// per-voxel arithmetic as voxelize_body -- coordinates from the packed grid or
+// per-voxel arithmetic as camera_sum (fvp_layout.h) -- coordinates from the packed grid or
 // projected on the fly, setup_taps, fma(d,w3, fma(c,w2, fma(b,w1, a*w0))) per
 // camera in view order with the 16-camera block fold, + 0 / + blocks, / V,
 // clamp -- hence bit-identical to the cube's voxels.  The heatmaps are read
