@@ -31,6 +31,7 @@
 #include <climits>
 #include <type_traits>
 
+#include "fvp_frames.h"  // uint8 frame sources of the u8 stems
 #include "fvp_layout.h"  // fvp_device.h, buffer descriptors (uniform_rsrc, kOOB)
 
 namespace fvp {
@@ -1003,31 +1004,16 @@ constexpr int kStemWP = 232;  // weight row pitch (bf16): 224 + 8, conflict-free
 constexpr int kStemOP = 72;   // output staging pitch (bf16)
 constexpr int kStemHE = (kStemHR * kStemHX + 255) / 256;  // halo pixels per thread
 
-__global__ __launch_bounds__(256, 2) void conv_stem7_bf16_kernel(const float *__restrict__ img, int C, int H, int W,
-                                                                  int Ho, int Wo, int tiles_x, int tiles_y,
-                                                                  int ntiles, const __bf16 *__restrict__ wpk,
-                                                                  const float *__restrict__ scale,
-                                                                  const float *__restrict__ shift,
-                                                                  __bf16 *__restrict__ out) {
-    constexpr int HALO_B = kStemHR * kStemHX * 8, W_B = 64 * kStemWP * 2;
-    constexpr int OUT_B = kStemTH * kStemTW * kStemOP * 2;
-    __shared__ __attribute__((aligned(16))) unsigned char smem[HALO_B + W_B + OUT_B];
-    __bf16 *halo = reinterpret_cast<__bf16 *>(smem);
-    __bf16 *wl = reinterpret_cast<__bf16 *>(smem + HALO_B);
-    __bf16 *st = reinterpret_cast<__bf16 *>(smem + HALO_B + W_B);
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int px = lane & 31, h = lane >> 5;
-    const int per_img = tiles_x * tiles_y;
-    // weights [64][224] -> LDS rows of kStemWP, once per block
-    for (int e = t; e < 64 * 28; e += 256) {
-        const int co = e / 28, q = e - (e / 28) * 28;
-        *reinterpret_cast<uint4 *>(wl + co * kStemWP + q * 8) = *reinterpret_cast<const uint4 *>(wpk + co * 224 + q * 8);
-    }
+// What differs between the stem's variants is its halo loader: what a thread
+// keeps in registers for the next tile (load) and how that reaches LDS as
+// [row][x][4 channels] bf16 (store).  The weights, the MFMA loop and the
+// epilogue are conv_stem7_bf16_body for all of them.
+struct StemPlanarHalo {  // NCHW fp32 planes
+    const float *__restrict__ img;
+    int C, H, W;
     float hv[kStemHE][3];  // the next tile's halo pixels (up to 3 planes; a 4th would be a C = 4 input)
     float hv4[kStemHE];
-    auto load_halo = [&](int tile) {
-        const int n = tile / per_img, tr = tile - n * per_img;
-        const int iy0 = 2 * ((tr / tiles_x) * kStemTH) - 3, ix0 = 2 * ((tr - (tr / tiles_x) * tiles_x) * kStemTW) - 3;
+    __device__ __forceinline__ void load(int n, int iy0, int ix0, int t) {
         const float *__restrict__ src = img + (size_t)n * C * H * W;
 #pragma unroll
         for (int u = 0; u < kStemHE; ++u) {
@@ -1040,11 +1026,8 @@ __global__ __launch_bounds__(256, 2) void conv_stem7_bf16_kernel(const float *__
             for (int ch = 0; ch < 3; ++ch) hv[u][ch] = (in && ch < C) ? src[(size_t)ch * H * W + o] : 0.0f;
             hv4[u] = (in && C > 3) ? src[(size_t)3 * H * W + o] : 0.0f;
         }
-    };
-    int tile = blockIdx.x;
-    if (tile < ntiles) load_halo(tile);
-    for (; tile < ntiles; tile += gridDim.x) {
-        // halo registers -> LDS (every wave finished the previous tile's MFMAs: barrier below)
+    }
+    __device__ __forceinline__ void store(__bf16 *halo, int t) const {
 #pragma unroll
         for (int u = 0; u < kStemHE; ++u) {
             const int e = t + u * 256;
@@ -1057,6 +1040,83 @@ __global__ __launch_bounds__(256, 2) void conv_stem7_bf16_kernel(const float *__
                 *reinterpret_cast<bf16x4 *>(halo + e * 4) = hb;
             }
         }
+    }
+};
+
+// uint8 frames (fvp_frames.h): a pixel's three bytes by output channel, left as
+// loaded until store -- anything computed from them here (packing them, a
+// select) would wait for the loads before the MFMAs instead of under them.  A
+// pixel outside the image reads the view's pixel (0, 0) and is cleared by its
+// bit of `inside`: it stays the conv's zero padding, not the normalised byte 0.
+// The table turns the bytes into the fp32 values the planar loader would have
+// read, then the same rounding to bf16.
+struct StemFrameHalo {
+    const FrameSrc &s;
+    const float *tab;  // LDS, kFrameTab floats
+    unsigned char hb[kStemHE][3];
+    unsigned inside;  // bit u: halo pixel t + 256 u is in the image
+    __device__ __forceinline__ void load(int n, int iy0, int ix0, int t) {
+        const unsigned char *__restrict__ src = frame_view(s, n);
+        const int k0 = s.swap_rb ? 2 : 0, k2 = 2 - k0;
+        inside = 0;
+#pragma unroll
+        for (int u = 0; u < kStemHE; ++u) {
+            const int e = t + u * 256;
+            const int r = e / kStemHX, c = e - (e / kStemHX) * kStemHX;
+            const int y = iy0 + r, x = ix0 + c;
+            const bool in = e < kStemHR * kStemHX && (unsigned)y < (unsigned)s.H && (unsigned)x < (unsigned)s.W;
+            const unsigned char *px = src + (in ? y : 0) * s.row_stride + (long long)(in ? x : 0) * s.pix_stride;
+            inside |= (unsigned)in << u;
+            hb[u][0] = px[k0];
+            hb[u][1] = px[1];
+            hb[u][2] = px[k2];
+        }
+    }
+    __device__ __forceinline__ void store(__bf16 *halo, int t) const {
+#pragma unroll
+        for (int u = 0; u < kStemHE; ++u) {
+            const int e = t + u * 256;
+            if (e < kStemHR * kStemHX) {
+                const bool in = (inside >> u) & 1;
+                bf16x4 o;
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) o[ch] = (__bf16)(in ? tab[ch * 256 + hb[u][ch]] : 0.0f);
+                o[3] = (__bf16)0.0f;
+                *reinterpret_cast<bf16x4 *>(halo + e * 4) = o;
+            }
+        }
+    }
+};
+
+constexpr int kStemLdsB = kStemHR * kStemHX * 8 + 64 * kStemWP * 2 + kStemTH * kStemTW * kStemOP * 2;
+
+template <class Halo>
+__device__ __forceinline__ void conv_stem7_bf16_body(Halo &hl, unsigned char *smem, int Ho, int Wo, int tiles_x,
+                                                     int tiles_y, int ntiles, const __bf16 *__restrict__ wpk,
+                                                     const float *__restrict__ scale,
+                                                     const float *__restrict__ shift, __bf16 *__restrict__ out) {
+    constexpr int HALO_B = kStemHR * kStemHX * 8, W_B = 64 * kStemWP * 2;
+    __bf16 *halo = reinterpret_cast<__bf16 *>(smem);
+    __bf16 *wl = reinterpret_cast<__bf16 *>(smem + HALO_B);
+    __bf16 *st = reinterpret_cast<__bf16 *>(smem + HALO_B + W_B);
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int px = lane & 31, h = lane >> 5;
+    const int per_img = tiles_x * tiles_y;
+    // weights [64][224] -> LDS rows of kStemWP, once per block
+    for (int e = t; e < 64 * 28; e += 256) {
+        const int co = e / 28, q = e - (e / 28) * 28;
+        *reinterpret_cast<uint4 *>(wl + co * kStemWP + q * 8) = *reinterpret_cast<const uint4 *>(wpk + co * 224 + q * 8);
+    }
+    auto load_halo = [&](int tile) {
+        const int n = tile / per_img, tr = tile - n * per_img;
+        const int iy0 = 2 * ((tr / tiles_x) * kStemTH) - 3, ix0 = 2 * ((tr - (tr / tiles_x) * tiles_x) * kStemTW) - 3;
+        hl.load(n, iy0, ix0, t);
+    };
+    int tile = blockIdx.x;
+    if (tile < ntiles) load_halo(tile);
+    for (; tile < ntiles; tile += gridDim.x) {
+        // halo registers -> LDS (every wave finished the previous tile's MFMAs: barrier below)
+        hl.store(halo, t);
         __syncthreads();
         const int n = tile / per_img, tr = tile - n * per_img;
         const int oy0 = (tr / tiles_x) * kStemTH, ox0 = (tr - (tr / tiles_x) * tiles_x) * kStemTW;
@@ -1123,6 +1183,33 @@ __global__ __launch_bounds__(256, 2) void conv_stem7_bf16_kernel(const float *__
     }
 }
 
+__global__ __launch_bounds__(256, 2) void conv_stem7_bf16_kernel(const float *__restrict__ img, int C, int H, int W,
+                                                                  int Ho, int Wo, int tiles_x, int tiles_y,
+                                                                  int ntiles, const __bf16 *__restrict__ wpk,
+                                                                  const float *__restrict__ scale,
+                                                                  const float *__restrict__ shift,
+                                                                  __bf16 *__restrict__ out) {
+    __shared__ __attribute__((aligned(16))) unsigned char smem[kStemLdsB];
+    StemPlanarHalo hl{img, C, H, W};
+    conv_stem7_bf16_body(hl, smem, Ho, Wo, tiles_x, tiles_y, ntiles, wpk, scale, shift, out);
+}
+
+// The stem straight from uint8 frames (fvp_conv_stem7_u8_bf16): the block builds the
+// normalisation table behind the stem's LDS, everything else is the kernel above.
+__global__ __launch_bounds__(256, 2) void conv_stem7_u8_bf16_kernel(FrameSrc src, int Ho, int Wo, int tiles_x,
+                                                                     int tiles_y, int ntiles,
+                                                                     const __bf16 *__restrict__ wpk,
+                                                                     const float *__restrict__ scale,
+                                                                     const float *__restrict__ shift,
+                                                                     __bf16 *__restrict__ out) {
+    __shared__ __attribute__((aligned(16))) unsigned char smem[kStemLdsB + kFrameTab * 4];
+    float *tab = reinterpret_cast<float *>(smem + kStemLdsB);
+    frame_table(tab, src, threadIdx.x, 256);
+    __syncthreads();  // the first halo store reads the table
+    StemFrameHalo hl{src, tab};
+    conv_stem7_bf16_body(hl, smem, Ho, Wo, tiles_x, tiles_y, ntiles, wpk, scale, shift, out);
+}
+
 // ---- the same stem on the fp32 matrix cores (the default precision) --------
 // 7x7 / s2 / p3, C <= 3 NCHW planes -> 64 channels + BN + ReLU, fp32 NHWC64
 // out.  The generic path converts the images to a 4-channel NHWC pitch first
@@ -1146,30 +1233,14 @@ constexpr int kS32HU = (kS32Halo + 255) / 256;               // halo floats per 
 constexpr int kS32K = 148, kS32WP = 80;                      // weight rows [kk][co], conflict-free pitch
 constexpr int kS32HaloLds = (kS32Halo + 3) / 4 * 4;
 
-__global__ __launch_bounds__(256, 2) void conv_stem7_f32_kernel(const float *__restrict__ img, int C, int H, int W,
-                                                                 int Ho, int Wo, int tiles_x, int tiles_y,
-                                                                 int ntiles, const float *__restrict__ wpk,
-                                                                 const float *__restrict__ scale,
-                                                                 const float *__restrict__ shift,
-                                                                 float *__restrict__ out) {
-    __shared__ __attribute__((aligned(16))) float lds[kS32HaloLds + kS32K * kS32WP];
-    float *halo = lds, *wl = lds + kS32HaloLds;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int j = lane & 15, g = lane >> 4;
-    const int per_img = tiles_x * tiles_y;
-    for (int e = t; e < kS32K * kS32WP / 4; e += 256)
-        reinterpret_cast<f32x4 *>(wl)[e] = reinterpret_cast<const f32x4 *>(wpk)[e];
+// The halo loaders, as for the bf16 stem: load keeps the next tile's halo in
+// registers, store puts it into LDS as [row][x][c] fp32.
+struct S32PlanarHalo {  // NCHW fp32 planes
+    const float *__restrict__ img;
+    int C, H, W;
     float hv[kS32HU];
-    auto origin = [&](int tile, int &n, int &oy0, int &ox0) {
-        n = tile / per_img;
-        const int tr = tile - n * per_img, ty = tr / tiles_x;
-        oy0 = ty * kS32TH;
-        ox0 = (tr - ty * tiles_x) * kS32TW;
-    };
     // halo float e <- plane c = e / (HR * HX), row r, column x (consecutive threads: consecutive x)
-    auto load_halo = [&](int tile) {
-        int n, oy0, ox0;
-        origin(tile, n, oy0, ox0);
+    __device__ __forceinline__ void load(int n, int oy0, int ox0, int t) {
         const float *__restrict__ src = img + (size_t)n * C * H * W;
 #pragma unroll
         for (int u = 0; u < kS32HU; ++u) {
@@ -1180,6 +1251,76 @@ __global__ __launch_bounds__(256, 2) void conv_stem7_f32_kernel(const float *__r
             const bool in = e < kS32Halo && c < C && (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W;
             hv[u] = in ? src[((size_t)c * H + y) * W + x] : 0.0f;
         }
+    }
+    __device__ __forceinline__ void store(float *halo, int t) const {
+#pragma unroll
+        for (int u = 0; u < kS32HU; ++u) {
+            const int e = t + 256 * u;
+            if (e < kS32Halo) {
+                const int c = e / (kS32HR * kS32HX), rem = e - c * (kS32HR * kS32HX);
+                halo[rem * 3 + c] = hv[u];  // [row][x][c]: row * 207 + x * 3 + c = rem * 3 + c
+            }
+        }
+    }
+};
+
+// uint8 frames (fvp_frames.h).  HWC is the LDS order, so halo float e is byte
+// e - 207 r of a 207-byte run of source row r (3-byte pixels, no swap; else the
+// same bytes picked per pixel): consecutive threads read consecutive bytes and
+// write consecutive LDS words.  A register holds the byte, or -1 outside the
+// image: that element is the conv's zero padding, not the normalised byte 0.
+struct S32FrameHalo {
+    const FrameSrc &s;
+    const float *tab;  // LDS, kFrameTab floats
+    int hb[kS32HU];
+    __device__ __forceinline__ void load(int n, int oy0, int ox0, int t) {
+        const unsigned char *__restrict__ src = frame_view(s, n);
+#pragma unroll
+        for (int u = 0; u < kS32HU; ++u) {
+            const int e = t + 256 * u;
+            const int r = e / kS32RP, rem = e - r * kS32RP;
+            const int xx = rem / 3, c = rem - 3 * xx;
+            const int y = 2 * oy0 - 3 + r, x = 2 * ox0 - 3 + xx;
+            const bool in = e < kS32Halo && (unsigned)y < (unsigned)s.H && (unsigned)x < (unsigned)s.W;
+            const int k = s.swap_rb ? 2 - c : c;
+            hb[u] = in ? (int)src[y * s.row_stride + (long long)x * s.pix_stride + k] : -1;
+        }
+    }
+    __device__ __forceinline__ void store(float *halo, int t) const {
+#pragma unroll
+        for (int u = 0; u < kS32HU; ++u) {
+            const int e = t + 256 * u;
+            if (e < kS32Halo) {
+                const int rem = e - (e / kS32RP) * kS32RP, c = rem - 3 * (rem / 3);
+                halo[e] = hb[u] >= 0 ? tab[c * 256 + (hb[u] & 255)] : 0.0f;
+            }
+        }
+    }
+};
+
+constexpr int kS32Lds = kS32HaloLds + kS32K * kS32WP;  // floats
+
+template <class Halo>
+__device__ __forceinline__ void conv_stem7_f32_body(Halo &hl, float *lds, int Ho, int Wo, int tiles_x, int tiles_y,
+                                                    int ntiles, const float *__restrict__ wpk,
+                                                    const float *__restrict__ scale,
+                                                    const float *__restrict__ shift, float *__restrict__ out) {
+    float *halo = lds, *wl = lds + kS32HaloLds;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int j = lane & 15, g = lane >> 4;
+    const int per_img = tiles_x * tiles_y;
+    for (int e = t; e < kS32K * kS32WP / 4; e += 256)
+        reinterpret_cast<f32x4 *>(wl)[e] = reinterpret_cast<const f32x4 *>(wpk)[e];
+    auto origin = [&](int tile, int &n, int &oy0, int &ox0) {
+        n = tile / per_img;
+        const int tr = tile - n * per_img, ty = tr / tiles_x;
+        oy0 = ty * kS32TH;
+        ox0 = (tr - ty * tiles_x) * kS32TW;
+    };
+    auto load_halo = [&](int tile) {
+        int n, oy0, ox0;
+        origin(tile, n, oy0, ox0);
+        hl.load(n, oy0, ox0, t);
     };
     f32x4 sc[4], sh[4];
 #pragma unroll
@@ -1195,14 +1336,7 @@ __global__ __launch_bounds__(256, 2) void conv_stem7_f32_kernel(const float *__r
     if (tile < ntiles) load_halo(tile);
     for (; tile < ntiles; tile += gridDim.x) {
         __syncthreads();  // every wave is past the previous tile's halo reads (and the weights are stored)
-#pragma unroll
-        for (int u = 0; u < kS32HU; ++u) {
-            const int e = t + 256 * u;
-            if (e < kS32Halo) {
-                const int c = e / (kS32HR * kS32HX), rem = e - c * (kS32HR * kS32HX);
-                halo[rem * 3 + c] = hv[u];  // [row][x][c]: row * 207 + x * 3 + c = rem * 3 + c
-            }
-        }
+        hl.store(halo, t);
         if (tile + (int)gridDim.x < ntiles) load_halo(tile + gridDim.x);  // in flight during the MFMAs
         __syncthreads();
         f32x4 acc[4][4];
@@ -1245,6 +1379,33 @@ __global__ __launch_bounds__(256, 2) void conv_stem7_f32_kernel(const float *__r
             }
         }
     }
+}
+
+__global__ __launch_bounds__(256, 2) void conv_stem7_f32_kernel(const float *__restrict__ img, int C, int H, int W,
+                                                                 int Ho, int Wo, int tiles_x, int tiles_y,
+                                                                 int ntiles, const float *__restrict__ wpk,
+                                                                 const float *__restrict__ scale,
+                                                                 const float *__restrict__ shift,
+                                                                 float *__restrict__ out) {
+    __shared__ __attribute__((aligned(16))) float lds[kS32Lds];
+    S32PlanarHalo hl{img, C, H, W};
+    conv_stem7_f32_body(hl, lds, Ho, Wo, tiles_x, tiles_y, ntiles, wpk, scale, shift, out);
+}
+
+// The stem straight from uint8 frames (fvp_conv_stem7_u8_f32): a tile's halo is 4,347
+// source bytes instead of 17,388, and no normalise pass writes and re-reads fp32 views.
+__global__ __launch_bounds__(256, 2) void conv_stem7_u8_f32_kernel(FrameSrc src, int Ho, int Wo, int tiles_x,
+                                                                    int tiles_y, int ntiles,
+                                                                    const float *__restrict__ wpk,
+                                                                    const float *__restrict__ scale,
+                                                                    const float *__restrict__ shift,
+                                                                    float *__restrict__ out) {
+    __shared__ __attribute__((aligned(16))) float lds[kS32Lds + kFrameTab];
+    float *tab = lds + kS32Lds;
+    frame_table(tab, src, threadIdx.x, 256);
+    __syncthreads();
+    S32FrameHalo hl{src, tab};
+    conv_stem7_f32_body(hl, lds, Ho, Wo, tiles_x, tiles_y, ntiles, wpk, scale, shift, out);
 }
 
 // ---- the CNNs' 7x7 J -> 16 front conv on bf16 MFMA, from the NCHW maps -------
@@ -2389,19 +2550,28 @@ extern "C" int fvp_nchw_to_nhwc(const float *in, int N, int C, int H, int W, int
     return (int)hipGetLastError();
 }
 
-extern "C" int fvp_conv_stem7_bf16(const float *img, int N, int C, int H, int W, const void *wpack, const float *scale,
-                                   const float *shift, void *out, void *stream) {
-    if (!img || !wpack || !scale || !shift || !out) return FVP_ERR_NULL;
-    if (N <= 0 || C < 1 || C > 4 || H < 1 || W < 1) return FVP_ERR_SHAPE;
-    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;  // (H + 2*3 - 7) / 2 + 1
-    const int tx = (Wo + fvp::kStemTW - 1) / fvp::kStemTW, ty = (Ho + fvp::kStemTH - 1) / fvp::kStemTH;
-    if ((long long)N * tx * ty > 0x7fffffffLL) return FVP_ERR_SHAPE;
-    const int ntiles = N * tx * ty;
+// Launch shape of the stems (7x7 / s2 / p3 on 8 x 32 output tiles, both precisions):
+// persistent blocks, 2 per CU, walk the tiles.  false: more tiles than INT_MAX.
+static bool stem7_shape(int N, int H, int W, int *Ho, int *Wo, int *tx, int *ty, int *ntiles, int *blocks) {
+    static_assert(fvp::kStemTW == fvp::kS32TW && fvp::kStemTH == fvp::kS32TH, "one tile shape");
+    *Ho = (H - 1) / 2 + 1, *Wo = (W - 1) / 2 + 1;  // (H + 2*3 - 7) / 2 + 1
+    *tx = (*Wo + fvp::kStemTW - 1) / fvp::kStemTW, *ty = (*Ho + fvp::kStemTH - 1) / fvp::kStemTH;
+    if ((long long)N * *tx * *ty > 0x7fffffffLL) return false;
+    *ntiles = N * *tx * *ty;
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) != hipSuccess ||
         hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
         cus = 256;
-    const int blocks = ntiles < 2 * cus ? ntiles : 2 * cus;  // persistent: 2 blocks per CU walk the tiles
+    *blocks = *ntiles < 2 * cus ? *ntiles : 2 * cus;
+    return true;
+}
+
+extern "C" int fvp_conv_stem7_bf16(const float *img, int N, int C, int H, int W, const void *wpack, const float *scale,
+                                   const float *shift, void *out, void *stream) {
+    if (!img || !wpack || !scale || !shift || !out) return FVP_ERR_NULL;
+    if (N <= 0 || C < 1 || C > 4 || H < 1 || W < 1) return FVP_ERR_SHAPE;
+    int Ho, Wo, tx, ty, ntiles, blocks;
+    if (!stem7_shape(N, H, W, &Ho, &Wo, &tx, &ty, &ntiles, &blocks)) return FVP_ERR_SHAPE;
     hipLaunchKernelGGL(fvp::conv_stem7_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, img, C,
                        H, W, Ho, Wo, tx, ty, ntiles, reinterpret_cast<const __bf16 *>(wpack), scale, shift,
                        reinterpret_cast<__bf16 *>(out));
@@ -2413,17 +2583,42 @@ extern "C" int fvp_conv_stem7_f32(const float *img, int N, int C, int H, int W, 
     if (!img || !wpack || !scale || !shift || !out) return FVP_ERR_NULL;
     if (N <= 0 || C < 1 || C > 3 || H < 1 || W < 1) return FVP_ERR_SHAPE;
     if (((uintptr_t)wpack | (uintptr_t)scale | (uintptr_t)shift | (uintptr_t)out) & 15) return FVP_ERR_SHAPE;
-    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;  // (H + 2*3 - 7) / 2 + 1
-    const int tx = (Wo + fvp::kS32TW - 1) / fvp::kS32TW, ty = (Ho + fvp::kS32TH - 1) / fvp::kS32TH;
-    if ((long long)N * tx * ty > 0x7fffffffLL) return FVP_ERR_SHAPE;
-    const int ntiles = N * tx * ty;
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-        cus = 256;
-    const int blocks = ntiles < 2 * cus ? ntiles : 2 * cus;  // persistent: 2 blocks per CU walk the tiles
+    int Ho, Wo, tx, ty, ntiles, blocks;
+    if (!stem7_shape(N, H, W, &Ho, &Wo, &tx, &ty, &ntiles, &blocks)) return FVP_ERR_SHAPE;
     hipLaunchKernelGGL(fvp::conv_stem7_f32_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, img, C,
                        H, W, Ho, Wo, tx, ty, ntiles, wpack, scale, shift, out);
+    return (int)hipGetLastError();
+}
+
+extern "C" int fvp_conv_stem7_u8_bf16(const void *frames, int B, const fvp_frame_spec *spec, const void *wpack,
+                                      const float *scale, const float *shift, void *out, void *stream) {
+    if (!frames || !spec || !wpack || !scale || !shift || !out) return FVP_ERR_NULL;
+    fvp::FrameSrc src;
+    int N = 0;
+    const int st = fvp::frame_src(frames, B, spec, &src, &N);
+    if (st != FVP_OK) return st;
+    // the 16-B LDS copies of the weights and the 16-B scale / shift / output accesses
+    if (((uintptr_t)wpack | (uintptr_t)scale | (uintptr_t)shift | (uintptr_t)out) & 15) return FVP_ERR_SHAPE;
+    int Ho, Wo, tx, ty, ntiles, blocks;
+    if (!stem7_shape(N, src.H, src.W, &Ho, &Wo, &tx, &ty, &ntiles, &blocks)) return FVP_ERR_SHAPE;
+    hipLaunchKernelGGL(fvp::conv_stem7_u8_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, src,
+                       Ho, Wo, tx, ty, ntiles, reinterpret_cast<const __bf16 *>(wpack), scale, shift,
+                       reinterpret_cast<__bf16 *>(out));
+    return (int)hipGetLastError();
+}
+
+extern "C" int fvp_conv_stem7_u8_f32(const void *frames, int B, const fvp_frame_spec *spec, const float *wpack,
+                                     const float *scale, const float *shift, float *out, void *stream) {
+    if (!frames || !spec || !wpack || !scale || !shift || !out) return FVP_ERR_NULL;
+    fvp::FrameSrc src;
+    int N = 0;
+    const int st = fvp::frame_src(frames, B, spec, &src, &N);
+    if (st != FVP_OK) return st;
+    if (((uintptr_t)wpack | (uintptr_t)scale | (uintptr_t)shift | (uintptr_t)out) & 15) return FVP_ERR_SHAPE;
+    int Ho, Wo, tx, ty, ntiles, blocks;
+    if (!stem7_shape(N, src.H, src.W, &Ho, &Wo, &tx, &ty, &ntiles, &blocks)) return FVP_ERR_SHAPE;
+    hipLaunchKernelGGL(fvp::conv_stem7_u8_f32_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, src,
+                       Ho, Wo, tx, ty, ntiles, wpack, scale, shift, out);
     return (int)hipGetLastError();
 }
 

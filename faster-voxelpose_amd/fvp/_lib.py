@@ -32,6 +32,13 @@ class PersonSpec(ctypes.Structure):
                 ("whole_size", c_float * 3), ("ind_size", c_float * 3), ("bins", ctypes.c_int32 * 3)]
 
 
+class FrameSpec(ctypes.Structure):
+    _fields_ = [("H", ctypes.c_int32), ("W", ctypes.c_int32), ("VR", ctypes.c_int32), ("VC", ctypes.c_int32),
+                ("frame_stride", ctypes.c_int64), ("vr_stride", ctypes.c_int64), ("vc_stride", ctypes.c_int64),
+                ("row_stride", ctypes.c_int64), ("pix_stride", ctypes.c_int32), ("swap_rb", ctypes.c_int32),
+                ("mean", c_float * 3), ("std", c_float * 3)]
+
+
 # name -> argtypes (restype is int status for all but the two info calls)
 SIGNATURES = {
     "fvp_abi_version": [],
@@ -115,6 +122,11 @@ SIGNATURES = {
     "fvp_conv_front7_bf16": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "fvp_conv_stem7_bf16": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "fvp_conv_stem7_f32": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "fvp_frames_to_views": [c_void_p, c_int, ctypes.POINTER(FrameSpec), c_void_p, c_void_p],
+    "fvp_conv_stem7_u8_f32": [c_void_p, c_int, ctypes.POINTER(FrameSpec), c_void_p, c_void_p, c_void_p, c_void_p,
+                              c_void_p],
+    "fvp_conv_stem7_u8_bf16": [c_void_p, c_int, ctypes.POINTER(FrameSpec), c_void_p, c_void_p, c_void_p, c_void_p,
+                               c_void_p],
     "fvp_maxpool_pad_nhwc_bf16": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
     "fvp_maxpool2_nhwc": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
     "fvp_maxpool_nhwc": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p],

@@ -24,10 +24,15 @@ voxelize gather reads (``fvp_voxelize_cl``), so the views path needs no
 transpose pass (:meth:`FvpPoseResNet.heatmaps_cl`).  With
 ``heatmaps_cl(views, dtype=torch.float16)`` a 1x1 final layer writes the fp16
 channels-last layout of the fp16 gathers itself (``fvp_conv1x1_cl_f16``), so
-that route needs no cast pass either.  ``__call__`` returns the
+that route needs no cast pass either.  ``heatmaps_cl_frames`` takes uint8
+camera frames (fvp.frames.Frames) instead of normalised views: the 7x7 stem
+reads the bytes itself (``fvp_conv_stem7_u8_f32`` / ``_bf16``), bit for bit the
+stem on ``frames.views()``.  ``__call__`` returns the
 reference's NCHW heatmaps.  Eval mode only (BatchNorm with running statistics).
 """
 from __future__ import annotations
+
+import ctypes
 
 import torch
 import torch.nn as nn
@@ -124,6 +129,7 @@ class FvpPoseResNet:
             i += 3
         self.final = ConvLayer(module.final_layer, None, dtype, algo=algo)
         self.last_head_route = None  # the route of the last heatmaps_cl(dtype=torch.float16) (head_route)
+        self.last_frames_route = None  # the route of the last features_nhwc_frames (frames_route)
         self.num_joints = module.final_layer.out_channels
         # bf16: activations between the layers stay bf16 in HBM (half the bytes,
         # no per-chunk conversion), the stem's output and its max pool included;
@@ -155,6 +161,9 @@ class FvpPoseResNet:
             x = self._stem7_f32(images)
         else:
             x = self.stem(to_nhwc(images, RGB_PITCH), relu=True)
+        return self._after_stem(x)
+
+    def _after_stem(self, x: Act) -> Act:
         x = maxpool_pad(x, *self.pool)
         for b in self.blocks:
             x = b(x)
@@ -177,6 +186,30 @@ class FvpPoseResNet:
         _lib.call("fvp_conv_stem7_f32", _ptr(x), N, C, H, W, _ptr(self.stem7_f32), _ptr(self.stem.scale),
                   _ptr(self.stem.shift), _ptr(out), _stream(out))
         return Act(out, 64)
+
+    def frames_route(self) -> str:
+        """How features_nhwc_frames reads uint8 frames: "stem7_u8_bf16" / "stem7_u8_f32" -- the
+        7x7 stem kernel in use reads them itself (fvp_conv_stem7_u8_*, no normalise pass, bit for
+        bit the stem on frames.views()) -- or "views": frames.views() (fvp_frames_to_views) and
+        the existing path (a forced ``algo``, a stem that is not 7x7 / s2 / p3 -> 64)."""
+        return "stem7_u8_bf16" if self.stem7 is not None else "stem7_u8_f32" if self.stem7_f32 is not None else "views"
+
+    @torch.no_grad()
+    def features_nhwc_frames(self, frames) -> Act:
+        """features_nhwc on uint8 camera frames (fvp.frames.Frames), by the route frames_route
+        names (``last_frames_route`` afterwards)."""
+        if frames.device.type != "cuda":
+            raise _lib.FvpError(f"fvp: frames must be on a HIP device, got {frames.device}")
+        self.last_frames_route = route = self.frames_route()
+        if route == "views":
+            return self.features_nhwc(frames.views().flatten(0, 1))
+        bf16 = route == "stem7_u8_bf16"
+        out = torch.empty((frames.B * frames.V, (frames.H - 1) // 2 + 1, (frames.W - 1) // 2 + 1, 64),
+                          dtype=torch.bfloat16 if bf16 else torch.float32, device=frames.device)
+        _lib.call("fvp_conv_" + route, _ptr(frames.data), frames.B, ctypes.byref(frames.spec),
+                  _ptr(self.stem7 if bf16 else self.stem7_f32), _ptr(self.stem.scale), _ptr(self.stem.shift),
+                  _ptr(out), _stream(out))
+        return self._after_stem(Act(out, 64))
 
     def __call__(self, images: torch.Tensor) -> torch.Tensor:
         """ResNet.forward (resnet.py:187-201): [N,3,H,W] -> [N,J,h,w] fp32."""
@@ -205,10 +238,22 @@ class FvpPoseResNet:
             raise _lib.FvpError(f"fvp: heatmaps_cl: dtype must be None, torch.float32 or torch.float16, got {dtype}")
         B, V = views.shape[:2]
         images = views.reshape((B * V,) + tuple(views.shape[2:]))
+        return self._heatmaps_cl(self.features_nhwc(images), B, V, dtype)
+
+    @torch.no_grad()
+    def heatmaps_cl_frames(self, frames, dtype: torch.dtype | None = None) -> ChannelsLastHeatmaps:
+        """heatmaps_cl on uint8 camera frames (fvp.frames.Frames): equal to
+        heatmaps_cl(frames.views(), dtype) bit for bit, with the stem reading the frames where
+        frames_route allows (``last_frames_route`` afterwards)."""
+        if dtype not in (None, torch.float32, torch.float16):
+            raise _lib.FvpError(f"fvp: heatmaps_cl_frames: dtype must be None, torch.float32 or torch.float16, "
+                                f"got {dtype}")
+        return self._heatmaps_cl(self.features_nhwc_frames(frames), frames.B, frames.V, dtype)
+
+    def _heatmaps_cl(self, x: Act, B: int, V: int, dtype) -> ChannelsLastHeatmaps:
         if dtype != torch.float16:
-            act = self.forward_nhwc(images)
+            act = self.final(x, relu=False)
             return ChannelsLastHeatmaps(act.t.view(B, V, act.H, act.W, act.Cp), self.num_joints)
-        x = self.features_nhwc(images)
         self.last_head_route = self.head_route(x)
         if self.last_head_route == "cast":
             act = self.final(x, relu=False)

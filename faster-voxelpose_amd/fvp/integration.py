@@ -44,6 +44,7 @@ import torch
 from . import _lib
 from . import backbone as fvp_backbone
 from . import cnn as fvp_cnn
+from . import frames as fvp_frames
 from . import heatmaps as fvp_heatmaps
 from . import jln, project_individual, project_whole, proposal
 
@@ -272,14 +273,24 @@ def fused_fvp_forward(self, backbone=None, views=None, meta=None, targets=None, 
     path on the fvp backbone in eval mode: all B*V views in one pass, heatmaps
     written channels-last once (fp32, or fp16 with FvpOptions.heatmaps_dtype)
     and handed to the HDN / JLN gathers in place (fvp.heatmaps.attach);
-    everything after it is the reference's forward."""
+    everything after it is the reference's forward.  `views` may be uint8 camera
+    frames (fvp.frames.Frames): on the fvp backbone route the stem reads them
+    itself (FvpPoseResNet.heatmaps_cl_frames); every other route gets
+    views.views(), the tensor the reference would have been handed."""
     opts = options_of(self)
     attached = None
+    frames = views if isinstance(views, fvp_frames.Frames) else None
     if (views is not None and backbone is not None and not self.training and hasattr(backbone, "deconv_layers")
-            and _fvp_backbone_ok(backbone, views, opts)):
-        cl = fvp_backbone.cached(backbone, opts.backbone_dtype).heatmaps_cl(views, dtype=opts.heatmaps_dtype)
+            and _fvp_backbone_ok(backbone, views if frames is None else frames.data, opts)):
+        net = fvp_backbone.cached(backbone, opts.backbone_dtype)
+        if frames is not None:
+            cl = net.heatmaps_cl_frames(frames, dtype=opts.heatmaps_dtype)
+        else:
+            cl = net.heatmaps_cl(views, dtype=opts.heatmaps_dtype)
         input_heatmaps, views = cl.planar(), None  # [B,V,J,H,W], carrying the channels-last copy
         attached = input_heatmaps
+    elif frames is not None:
+        views = frames.views()
     try:
         return type(self)._fvp_original_forward(self, backbone=backbone, views=views, meta=meta, targets=targets,
                                                 input_heatmaps=input_heatmaps, cameras=cameras,

@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import collections
 import ctypes
+import math
 from typing import Optional
 
 import torch
@@ -920,3 +921,74 @@ def nms_topk_columns_joint(prob: torch.Tensor, K: int, cube: torch.Tensor):
         return nms_topk_columns(prob, K, cube)
     vals, flat = proposal_buffers(prob.shape[0], K, prob.device)
     return _nms_topk_columns_into(prob, K, cube, vals, flat)
+
+
+# ---------------------------------------------------------------------------
+# uint8 camera frames (include/fvp.h fvp_frame_spec; fvp/frames.py wraps these)
+def frame_spec(data: torch.Tensor, mosaic, swap_rb: bool, mean, std):
+    """The fvp_frame_spec of a uint8 tensor, from its strides (nothing is copied): per-view
+    ``[B,V,H,W,P]`` (mosaic None or empty) or a ``VR x VC`` mosaic ``[B,VR*H,VC*W,P]``, P = 3
+    or 4 bytes per pixel.  The last dimension needs stride 1 and the pixel stride must be P;
+    every other stride is free (a crop or a batch slice is read in place).
+    Returns (FrameSpec, B, V, H, W)."""
+    mosaic = tuple(int(v) for v in mosaic) if mosaic is not None else ()
+    if not isinstance(data, torch.Tensor) or data.dtype != torch.uint8:
+        raise _lib.FvpError(f"fvp: frames must be a uint8 tensor, got {getattr(data, 'dtype', type(data))}")
+    if len(mosaic) not in (0, 2) or any(v <= 0 for v in mosaic):
+        raise _lib.FvpError(f"fvp: mosaic must be None or (VR, VC) with positive entries, got {mosaic}")
+    if data.dim() != (4 if mosaic else 5):
+        raise _lib.FvpError(f"fvp: frames must be [B,V,H,W,3|4], or [B,VR*H,VC*W,3|4] with mosaic=(VR, VC); got "
+                            f"{tuple(data.shape)} with mosaic={mosaic or None}")
+    P, st = data.shape[-1], data.stride()
+    if P not in (3, 4):
+        raise _lib.FvpError(f"fvp: frames need 3 or 4 bytes per pixel, got {P}")
+    if mosaic:
+        VR, VC = mosaic
+        B, FH, FW = data.shape[:3]
+        if FH % VR or FW % VC:
+            raise _lib.FvpError(f"fvp: a {FH} x {FW} frame does not split into {VR} x {VC} views")
+        H, W = FH // VR, FW // VC
+        frame, row, pix = st[0], st[1], st[2]
+        vr, vc = H * row, W * P
+    else:
+        B, VR, H, W = data.shape[:4]
+        VC = 1
+        frame, vr, row, pix = st[0], st[1], st[2], st[3]
+        vc = 0
+    if min(B, VR, H, W) <= 0:
+        raise _lib.FvpError(f"fvp: empty frames {tuple(data.shape)}")
+    if st[-1] != 1 or pix != P:
+        raise _lib.FvpError(f"fvp: frames need interleaved pixels (last stride 1, pixel stride {P}), got strides {st}")
+    if row < W * P:
+        raise _lib.FvpError(f"fvp: frame rows overlap (row stride {row} < {W} pixels of {P} bytes)")
+    mean, std = [float(v) for v in mean], [float(v) for v in std]
+    if len(mean) != 3 or len(std) != 3:
+        raise _lib.FvpError("fvp: mean and std take one value per colour channel")
+    spec = _lib.FrameSpec(H, W, VR, VC, frame, vr, vc, row, P, int(bool(swap_rb)), _f3(mean), _f3(std))
+    for m, s in zip(spec.mean, spec.std):  # as fp32, the values the kernels divide by
+        if not (math.isfinite(m) and math.isfinite(s) and s != 0.0):
+            raise _lib.FvpError(f"fvp: mean must be finite and std finite and nonzero, got {mean}, {std}")
+    return spec, B, VR * VC, H, W
+
+
+@_custom_op("fvp::frames_to_views", mutates_args=(), device_types="cuda")
+def frames_to_views(data: torch.Tensor, mosaic: list[int], swap_rb: bool, mean: list[float],
+                    std: list[float]) -> torch.Tensor:
+    """uint8 frames (frame_spec's layouts; mosaic [] = per-view) -> the normalised views
+    [B,V,3,H,W] fp32 in one launch (fvp_frames_to_views), bit for bit
+    transforms.ToTensor() + transforms.Normalize(mean, std) on the CPU."""
+    if data.device.type != "cuda":
+        raise _lib.FvpError(f"fvp: frames must be on a HIP device, got {data.device}")
+    spec, B, V, H, W = frame_spec(data, mosaic, swap_rb, mean, std)
+    out = torch.empty((B, V, 3, H, W), dtype=torch.float32, device=data.device)
+    _lib.call("fvp_frames_to_views", _ptr(data), B, ctypes.byref(spec), _ptr(out), _stream(data))
+    return out
+
+
+@frames_to_views.register_fake
+def _(data, mosaic, swap_rb, mean, std):
+    if mosaic:
+        B, V, H, W = data.shape[0], mosaic[0] * mosaic[1], data.shape[1] // mosaic[0], data.shape[2] // mosaic[1]
+    else:
+        B, V, H, W = data.shape[:4]
+    return data.new_empty((B, V, 3, H, W), dtype=torch.float32)

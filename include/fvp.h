@@ -76,6 +76,27 @@ typedef struct fvp_person_spec {
     int32_t bins[3];      /* INDIVIDUAL_SPEC.VOXELS_PER_AXIS, e.g. 64,64,64 */
 } fvp_person_spec;
 
+/* uint8 camera frames as a decoder delivers them: B frames, each a VR x VC
+ * grid of H x W views of interleaved pixels (run/service.py:219-282 splits a
+ * 2 x 2 mosaic; lib/dataset/JointsDataset.py:194-199 reads one image per view).
+ * Byte k of pixel (y, x) of view v = r*VC + c of frame b is at
+ *   frames + b*frame_stride + r*vr_stride + c*vc_stride + y*row_stride + x*pix_stride + k.
+ * Per-view tensors [B][V][H][W][3]: VR = V, VC = 1, vr_stride = H*W*3; a mosaic
+ * [B][2H][2W][3]: VR = VC = 2, vr_stride = H*row_stride, vc_stride = W*3.  No
+ * alignment is required of the base pointer or of any stride.  Output channel
+ * c of a pixel is
+ *   ((float)byte[swap_rb ? 2 - c : c] / 255.0f - mean[c]) / std[c]
+ * in three rounded fp32 operations, both divisions IEEE-correct: bit for bit
+ * transforms.ToTensor() + transforms.Normalize(mean, std) on the CPU. */
+typedef struct fvp_frame_spec {
+    int32_t H, W;   /* one view */
+    int32_t VR, VC; /* views per frame as a VR x VC grid (split_frame order: TL, TR, BL, BR) */
+    int64_t frame_stride, vr_stride, vc_stride, row_stride; /* bytes; row_stride >= W*pix_stride */
+    int32_t pix_stride; /* 3, or 4 (BGRX / RGBX, the 4th byte ignored) */
+    int32_t swap_rb;    /* nonzero: cv2.cvtColor(BGR2RGB) of JointsDataset.py:196 */
+    float mean[3], std[3]; /* by output channel; finite, std nonzero */
+} fvp_frame_spec;
+
 int fvp_abi_version(void);
 const char *fvp_status_string(int status);
 
@@ -629,6 +650,22 @@ int fvp_conv_stem7_bf16(const float *img, int N, int C, int H, int W, const void
  * 4-channel-pitch conv of resnet.py:105-107 (fvp/backbone.py). */
 int fvp_conv_stem7_f32(const float *img, int N, int C, int H, int W, const float *wpack, const float *scale,
                        const float *shift, float *out, void *stream);
+/* uint8 frames -> the normalised fp32 views [B*VR*VC][3][H][W] the reference
+ * hands to backbone(views[:, c]) (faster_voxelpose.py:73-75), one launch, no
+ * workspace.  FVP_ERR_SHAPE: B, H, W, VR or VC <= 0, pix_stride not 3 or 4,
+ * row_stride < W*pix_stride, a zero or non-finite std, a non-finite mean, or
+ * more views / launch blocks than INT_MAX. */
+int fvp_frames_to_views(const void *frames, int B, const fvp_frame_spec *spec, float *views, void *stream);
+/* fvp_conv_stem7_f32 / fvp_conv_stem7_bf16 with N = B*VR*VC, C = 3, reading
+ * their halo from the uint8 frames: the same weight packing, alignment rules
+ * and outputs, bit for bit the stem run on fvp_frames_to_views' output (the
+ * conv's zero padding applies after the normalisation: a halo element outside
+ * the image is 0, not the normalised byte 0).  The spec checks are those of
+ * fvp_frames_to_views. */
+int fvp_conv_stem7_u8_f32(const void *frames, int B, const fvp_frame_spec *spec, const float *wpack,
+                          const float *scale, const float *shift, float *out, void *stream);
+int fvp_conv_stem7_u8_bf16(const void *frames, int B, const fvp_frame_spec *spec, const void *wpack,
+                           const float *scale, const float *shift, void *out, void *stream);
 /* The CNNs' front Basic2DBlock (cnns_2d.py: 7x7, stride 1, pad 3, C <= 16
  * planes -> 16 channels) + BN + ReLU on bf16 MFMA, straight from the NCHW
  * fp32 maps [N][C][H][W] to bf16 NHWC [N][H][W][16].  wpack: bf16
