@@ -872,18 +872,22 @@ class FvpCNN:
         hf = torch.zeros((32, 16), dtype=torch.float32, device=h.device)
         hf[:cout, :h.shape[0]] = h.t()
         wh = hf.reshape(2, 4, 4, 16).permute(0, 2, 3, 1).contiguous()  # [s][kq][j][c4]
-        return wd, c, wh, h.shape[0]
+        # the kernel reads the folded BN of all 32 y channels; the layer holds Cpo = 16 of them
+        # where Cout <= 16 (zeros past Cout either way: those channels of y stay 0)
+        sb = torch.zeros((2, 32), dtype=torch.float32, device=w.device)
+        sb[0, :c.Cpo], sb[1, :c.Cpo] = c.scale, c.shift
+        return wd, c, wh, h.shape[0], sb[0], sb[1]
 
     def _tail_nchw(self, x: Act, skip: Act):
         """decoder_upsample1(x) + skip, then the output layer, NCHW (fvp_up2_head_nchw);
         None where this input does not fit the kernel."""
-        wd, c, wh, J = self.tail
+        wd, c, wh, J, scale, shift = self.tail
         if (x.t.dtype != torch.float32 or skip.t.dtype != torch.float32 or x.Cp != c.Cpi or x.W % 32
                 or not x.t.is_contiguous() or not skip.t.is_contiguous() or skip.C > 32 or skip.C < c.Cout or skip.Cp % 4
                 or tuple(skip.t.shape[:3]) != (x.N, 2 * x.H, 2 * x.W)):
             return None
         out = torch.empty((x.N, J, 2 * x.H, 2 * x.W), dtype=torch.float32, device=x.t.device)
-        _lib.call("fvp_up2_head_nchw", _ptr(x.t), x.N, x.H, x.W, x.Cp, _ptr(wd), _ptr(c.scale), _ptr(c.shift),
+        _lib.call("fvp_up2_head_nchw", _ptr(x.t), x.N, x.H, x.W, x.Cp, _ptr(wd), _ptr(scale), _ptr(shift),
                   _ptr(skip.t), skip.Cp, c.Cout, _ptr(wh), _ptr(self.out.scale), _ptr(self.out.shift), J,
                   _ptr(out), _stream(out))
         return out

@@ -622,7 +622,8 @@ int fvp_conv1x1_nchw(const float *in, int N, int H, int W, int Cpi, int Cin, con
  * W % 32 == 0); skip: NHWC [N][2H][2W][Cps] (16-B aligned, Cps % 4 == 0); wd: [Cpi/16][4][128][4] with
  * wd[s][kq][(2 ry + rx) 32 + co][c4] = W[16 s + 4 c4 + kq][co][ry][rx] (zero past Cin / Cout);
  * wh: [2][4][16][4], wh[s][kq][j][c4] = Wh[j][16 s + 4 c4 + kq]; out: NCHW [N][J][2H][2W]
- * (fvp/cnn.py FvpCNN packs both). */
+ * (fvp/cnn.py FvpCNN packs both).  scale / shift: fp32 [32], all 32 read whatever Cs is (zero
+ * past Cout, so that those channels of y are 0); hscale / hshift: fp32 [J]. */
 int fvp_up2_head_nchw(const float *in, int N, int H, int W, int Cpi, const float *wd, const float *scale,
                       const float *shift, const float *skip, int Cps, int Cs, const float *wh, const float *hscale,
                       const float *hshift, int J, float *out, void *stream);
