@@ -30,6 +30,16 @@
 // The per-pixel value is fp32: expf(-(dx^2 + dy^2) * (float)(1 / (2 sigma^2)))
 // with the integer offsets from the window's centre pixel ul + floor(size / 2)
 // (which is often mu - 1, not mu: the reference's Gaussian sits on its patch).
+//
+// 'gt' heatmaps (fvp_render_poses3d, fvp_render_poses3d_f16): the same kernel
+// with POSE = true.  Its first loop, instead of reading 2-D keypoints, projects
+// the frame's 3-D joints through the view's fp64 camera and the resize
+// transform and applies the two visibility tests of JointsDataset.__getitem__
+// (lib/dataset/JointsDataset.py:221-259 with lib/utils/cameras.py:58-84 and
+// lib/utils/transforms.py:53-56) -- project_pose_point below, in the order
+// numpy evaluates them -- and keeps the visibility byte in LDS.  Everything after
+// that loop is the one body, so the result equals fvp_project_poses followed by
+// fvp_render_keypoints bit for bit.
 #include <math.h>
 
 #include <type_traits>
@@ -67,6 +77,61 @@ struct RenderArgs {
     int joints_f64, P, J, H, W, tiles_x, bands;
 };
 
+// The 'gt' operands: 3-D joints and flags shared by a frame's views, fp64 camera records in the
+// field order of the fp32 one (FVP_CAM_STRIDE), the 2x3 resize transform.
+struct PoseArgs {
+    const double *joints3d;      // [B][P][J][3]
+    const unsigned char *vis3d;  // [B][P][J] or null
+    const int *count;            // [B]
+    const double *cams;          // [S][V][FVP_CAM_STRIDE]
+    const int *cam_index;        // [B] or null
+    const double *resize_t;      // [2][3]
+    double *joints2d;            // [B][V][P][J][2] or null
+    unsigned char *vis2d;        // [B][V][P][J] or null
+    double ori_w1, ori_h1;       // ori_image_size - 1
+    double image_w, image_h;
+    int S, V;
+};
+
+struct RenderPoseArgs : RenderArgs {
+    PoseArgs pose;
+};
+
+// One joint through one camera: project_point_cpu (cameras.py:58-84), the original-image test
+// (JointsDataset.py:238-244), affine_transform (transforms.py:53-56) and the resized-image test
+// (JointsDataset.py:249-251).  fp64, one rounded operation per operator, fma() only where numpy's
+// matmul (3x3 by 3xJ) and dot (2x3 by [x, y, 1]) use one; NaN compares false as in numpy.  A
+// point behind the camera is not special-cased (the reference does not either).
+__device__ __forceinline__ bool project_pose_point(const double *X, bool vis3d, const double *cam, const PoseArgs &a,
+                                                   double &qx, double &qy) {
+    const double *t = a.resize_t;
+    const double d0 = X[0] - cam[9], d1 = X[1] - cam[10], d2 = X[2] - cam[11];
+    const double xc0 = fma(cam[2], d2, fma(cam[1], d1, cam[0] * d0));
+    const double xc1 = fma(cam[5], d2, fma(cam[4], d1, cam[3] * d0));
+    const double xc2 = fma(cam[8], d2, fma(cam[7], d1, cam[6] * d0));
+    const double den = xc2 + 1e-5;
+    const double y0 = xc0 / den, y1 = xc1 / den;
+    const double r = y0 * y0 + y1 * y1;
+    const double k0 = cam[16], k1 = cam[17], k2 = cam[18], p0 = cam[19], p1 = cam[20];
+    const double dd = ((1.0 + k0 * r) + (k1 * r) * r) + ((k2 * r) * r) * r;
+    const double u = (y0 * dd + ((2.0 * p0) * y0) * y1) + p1 * (r + (2.0 * y0) * y0);
+    const double w = (y1 * dd + ((2.0 * p1) * y0) * y1) + p0 * (r + (2.0 * y1) * y1);
+    const double px = cam[12] * u + cam[14], py = cam[13] * w + cam[15];
+    bool vis = vis3d && px >= 0.0 && px <= a.ori_w1 && py >= 0.0 && py <= a.ori_h1;
+    qx = fma(t[0], px, t[1] * py) + t[2];
+    qy = fma(t[3], px, t[4] * py) + t[5];
+    // np.min(pose[i]) < 0: a NaN coordinate makes the minimum NaN, which compares false
+    const bool neg = qx == qx && qy == qy && (qx < 0.0 || qy < 0.0);
+    if (neg || qx >= a.image_w || qy >= a.image_h) vis = false;
+    return vis;
+}
+
+// The camera record of frame b, view v: cam_index picks the frame's set (pinned into 0..S-1).
+__device__ __forceinline__ const double *pose_camera(const PoseArgs &a, int b, int v) {
+    const int set = a.cam_index ? min(max(a.cam_index[b], 0), a.S - 1) : 0;
+    return a.cams + ((long long)set * a.V + v) * FVP_CAM_STRIDE;
+}
+
 // Python's int(): truncation toward zero.  Values beyond +-2^30 pixels are
 // pinned there (a C conversion of them is undefined); such a window lies off
 // every heatmap either way.
@@ -87,8 +152,10 @@ struct RenderAcc<8> {
 };
 
 // JPL: joints (channels) per lane = per 16-B store: 4 fp32 or 8 fp16.
-template <int CP, int JPL>
-__global__ __launch_bounds__(kRenderThreads) void render_keypoints_kernel(const RenderArgs a) {
+// POSE: the records start from 3-D joints (a.pose) instead of a.joints / a.vis.
+template <int CP, int JPL, bool POSE = false>
+__global__ __launch_bounds__(kRenderThreads) void render_keypoints_kernel(
+    const std::conditional_t<POSE, RenderPoseArgs, RenderArgs> a) {
     constexpr int QP = CP / JPL;              // channel groups (one 16-B piece) per pixel
     constexpr int PPP = kRenderThreads / QP;  // pixels per pass
     constexpr int PASSES = kTileW * kBandH / PPP;
@@ -108,26 +175,59 @@ __global__ __launch_bounds__(kRenderThreads) void render_keypoints_kernel(const 
     RenderRec *recs = reinterpret_cast<RenderRec *>(q + nrec);           // [nrec]
     RenderPerson *pers = reinterpret_cast<RenderPerson *>(recs + nrec);  // [P]
     unsigned short *band = reinterpret_cast<unsigned short *>(pers + P);  // [nrec] records meeting the band
+    unsigned char *seen2d = reinterpret_cast<unsigned char *>(band + nrec);  // [nrec] 2-D visibility (POSE only)
 
-    const int cnt = min(max(a.count[bv], 0), P);
+    int cnt;
+    if constexpr (POSE)
+        cnt = min(max(a.pose.count[bv / a.pose.V], 0), P);
+    else
+        cnt = min(max(a.count[bv], 0), P);
     const int live = cnt * J;
     if (tid < 3 * QP) kept_n[tid / QP][tid % QP] = 0;
     if (tid == 0) band_n = 0;
 
-    // q = joint / stride for the rows below count (the padded rows are never read)
-    for (int r = tid; r < live; r += kRenderThreads) {
-        const long long e = ((long long)bv * nrec + r) * 2;
-        double jx, jy;
-        if (a.joints_f64) {
-            const double *src = reinterpret_cast<const double *>(a.joints);
-            jx = src[e];
-            jy = src[e + 1];
-        } else {
-            const float *src = reinterpret_cast<const float *>(a.joints);
-            jx = (double)src[e];
-            jy = (double)src[e + 1];
+    if constexpr (POSE) {
+        // q = project(joint3d) / stride; every band's block computes the same values, band 0 also
+        // writes the optional outputs (rows at or beyond count as zeros)
+        const PoseArgs &ps = a.pose;
+        const int b = bv / ps.V;
+        const double *cam = pose_camera(ps, b, bv - b * ps.V);
+        const bool emit = ty0 == 0 && (ps.joints2d != nullptr || ps.vis2d != nullptr);
+        for (int r = tid; r < (emit ? nrec : live); r += kRenderThreads) {
+            double qx = 0.0, qy = 0.0;
+            bool vis = false;
+            if (r < live) {
+                const long long e = (long long)b * nrec + r;
+                vis = project_pose_point(ps.joints3d + e * 3, ps.vis3d == nullptr || ps.vis3d[e] != 0, cam, ps, qx,
+                                         qy);
+                q[r] = make_double2(qx / a.stride_x, qy / a.stride_y);
+                seen2d[r] = vis ? 1 : 0;
+            }
+            if (emit) {
+                const long long o = (long long)bv * nrec + r;
+                if (ps.joints2d) {
+                    ps.joints2d[o * 2] = qx;
+                    ps.joints2d[o * 2 + 1] = qy;
+                }
+                if (ps.vis2d) ps.vis2d[o] = vis ? 1 : 0;
+            }
         }
-        q[r] = make_double2(jx / a.stride_x, jy / a.stride_y);
+    } else {
+        // q = joint / stride for the rows below count (the padded rows are never read)
+        for (int r = tid; r < live; r += kRenderThreads) {
+            const long long e = ((long long)bv * nrec + r) * 2;
+            double jx, jy;
+            if (a.joints_f64) {
+                const double *src = reinterpret_cast<const double *>(a.joints);
+                jx = src[e];
+                jy = src[e + 1];
+            } else {
+                const float *src = reinterpret_cast<const float *>(a.joints);
+                jx = (double)src[e];
+                jy = (double)src[e + 1];
+            }
+            q[r] = make_double2(jx / a.stride_x, jy / a.stride_y);
+        }
     }
     __syncthreads();
 
@@ -166,7 +266,11 @@ __global__ __launch_bounds__(kRenderThreads) void render_keypoints_kernel(const 
         rec.x0 = rec.x1 = rec.y0 = rec.y1 = rec.cx = rec.cy = 0;
         rec.inv = pr.inv;
         rec.j = j;
-        const bool seen = a.vis == nullptr || a.vis[(long long)bv * nrec + r] != 0;
+        bool seen;
+        if constexpr (POSE)
+            seen = seen2d[r] != 0;
+        else
+            seen = a.vis == nullptr || a.vis[(long long)bv * nrec + r] != 0;
         if (pr.ok && seen) {
             const int mux = trunc_int(q[r].x), muy = trunc_int(q[r].y);
             const int ulx = trunc_int((double)mux - pr.tmp), uly = trunc_int((double)muy - pr.tmp);
@@ -245,15 +349,63 @@ __global__ __launch_bounds__(kRenderThreads) void render_keypoints_kernel(const 
     }
 }
 
+// The projection alone: one thread per (frame, view, person, joint); rows at or beyond count are
+// written as zeros, so every element of both outputs is written.
+__global__ __launch_bounds__(kRenderThreads) void project_poses_kernel(const PoseArgs a, int nrec, int J,
+                                                                       long long total) {
+    const long long i = (long long)blockIdx.x * kRenderThreads + threadIdx.x;
+    if (i >= total) return;
+    const int bv = (int)(i / nrec), r = (int)(i - (long long)bv * nrec);
+    const int b = bv / a.V;
+    const int live = min(max(a.count[b], 0), nrec / J) * J;
+    double qx = 0.0, qy = 0.0;
+    bool vis = false;
+    if (r < live) {
+        const long long e = (long long)b * nrec + r;
+        vis = project_pose_point(a.joints3d + e * 3, a.vis3d == nullptr || a.vis3d[e] != 0,
+                                 pose_camera(a, b, bv - b * a.V), a, qx, qy);
+    }
+    a.joints2d[i * 2] = qx;
+    a.joints2d[i * 2 + 1] = qy;
+    a.vis2d[i] = vis ? 1 : 0;
+}
+
 }  // namespace fvp
 
 namespace fvp {
 
-// Host checks and the launch shared by the fp32 (half = false) and fp16 entry points.
-static int render_launch(const void *joints, int joints_f64, const int *count, const unsigned char *vis, int B, int V,
-                         int P, int J, int H, int W, double image_w, double image_h, double sigma, int Cp, void *out_cl,
-                         bool half, void *stream) {
-    if (!joints || !count || !out_cl) return FVP_ERR_NULL;
+// Host checks of the 'gt' operands shared by fvp_project_poses and fvp_render_poses3d(_f16).
+static int pose_args(const double *joints3d, const unsigned char *vis3d, const int *count, int B, int P, int J,
+                     const double *cams64, const int *cam_index, int S, int V, const double *resize_t64, double ori_w,
+                     double ori_h, double image_w, double image_h, double *joints2d, unsigned char *vis2d,
+                     PoseArgs *a) {
+    if (!joints3d || !count || !cams64 || !resize_t64) return FVP_ERR_NULL;
+    if (B <= 0 || P <= 0 || J <= 0 || J > kMaxRenderJ || P > kMaxRenderP) return FVP_ERR_SHAPE;
+    if (V <= 0 || V > FVP_MAX_VIEWS || S <= 0) return FVP_ERR_SHAPE;
+    if ((long long)B * V > 0x7fffffffLL) return FVP_ERR_SHAPE;  // 32-bit frame-view index
+    if (!(ori_w > 0.0) || !(ori_h > 0.0) || !(image_w > 0.0) || !(image_h > 0.0) || !isfinite(ori_w) ||
+        !isfinite(ori_h) || !isfinite(image_w) || !isfinite(image_h))
+        return FVP_ERR_SHAPE;
+    a->joints3d = joints3d;
+    a->vis3d = vis3d;
+    a->count = count;
+    a->cams = cams64;
+    a->cam_index = cam_index;
+    a->resize_t = resize_t64;
+    a->joints2d = joints2d;
+    a->vis2d = vis2d;
+    a->ori_w1 = ori_w - 1.0;
+    a->ori_h1 = ori_h - 1.0;
+    a->image_w = image_w;
+    a->image_h = image_h;
+    a->S = S;
+    a->V = V;
+    return FVP_OK;
+}
+
+// Fills the painter's part of the arguments after the host checks both launches share.
+static int render_args(int B, int V, int P, int J, int H, int W, double image_w, double image_h, double sigma, int Cp,
+                       void *out_cl, bool half, RenderArgs *a) {
     if (B <= 0 || V <= 0 || P <= 0 || J <= 0 || H <= 0 || W <= 0) return FVP_ERR_SHAPE;
     if (J > kMaxRenderJ || P > kMaxRenderP || Cp < J || Cp % 16 || Cp > 32) return FVP_ERR_SHAPE;
     if ((long long)H * W * Cp > 0x7fffffffLL) return FVP_ERR_SHAPE;  // 32-bit element offsets within a view
@@ -261,26 +413,69 @@ static int render_launch(const void *joints, int joints_f64, const int *count, c
         !isfinite(sigma))
         return FVP_ERR_SHAPE;
     if (half && (reinterpret_cast<uintptr_t>(out_cl) & 15)) return FVP_ERR_SHAPE;  // 16-B stores
+    a->out = out_cl;
+    a->stride_x = image_w / (double)W;  // feat_stride = image_size / heatmap_size
+    a->stride_y = image_h / (double)H;
+    a->sigma = sigma;
+    a->P = P;
+    a->J = J;
+    a->H = H;
+    a->W = W;
+    a->tiles_x = (W + kTileW - 1) / kTileW;
+    a->bands = (H + kBandH - 1) / kBandH;
+    if ((long long)B * V * a->bands > 0x7fffffffLL) return FVP_ERR_SHAPE;
+    return FVP_OK;
+}
+
+static size_t render_lds_bytes(int P, int J) {
+    return (size_t)P * J * (sizeof(double2) + sizeof(RenderRec) + sizeof(unsigned short)) +
+           (size_t)P * sizeof(RenderPerson);
+}
+
+// Host checks and the launch shared by fvp_render_poses3d (half = false) and fvp_render_poses3d_f16.
+static int render_poses_launch(const double *joints3d, const unsigned char *vis3d, const int *count, int B, int P,
+                               int J, const double *cams64, const int *cam_index, int S, int V,
+                               const double *resize_t64, double ori_w, double ori_h, double image_w, double image_h,
+                               int H, int W, double sigma, int Cp, void *out_cl, double *joints2d,
+                               unsigned char *vis2d, bool half, void *stream) {
+    if (!out_cl) return FVP_ERR_NULL;
+    RenderPoseArgs a;
+    int st = pose_args(joints3d, vis3d, count, B, P, J, cams64, cam_index, S, V, resize_t64, ori_w, ori_h, image_w,
+                       image_h, joints2d, vis2d, &a.pose);
+    if (st != FVP_OK) return st;
+    st = render_args(B, V, P, J, H, W, image_w, image_h, sigma, Cp, out_cl, half, &a);
+    if (st != FVP_OK) return st;
+    a.joints = nullptr;
+    a.count = nullptr;
+    a.vis = nullptr;
+    a.joints_f64 = 1;
+    const size_t lds = render_lds_bytes(P, J) + (size_t)P * J;  // + the 2-D visibility bytes
+    const dim3 grid((unsigned)((long long)B * V * a.bands)), block(kRenderThreads);
+    if (Cp == 16 && !half)
+        hipLaunchKernelGGL((render_keypoints_kernel<16, 4, true>), grid, block, lds, (hipStream_t)stream, a);
+    else if (!half)
+        hipLaunchKernelGGL((render_keypoints_kernel<32, 4, true>), grid, block, lds, (hipStream_t)stream, a);
+    else if (Cp == 16)
+        hipLaunchKernelGGL((render_keypoints_kernel<16, 8, true>), grid, block, lds, (hipStream_t)stream, a);
+    else
+        hipLaunchKernelGGL((render_keypoints_kernel<32, 8, true>), grid, block, lds, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+}
+
+// Host checks and the launch shared by the fp32 (half = false) and fp16 entry points.
+static int render_launch(const void *joints, int joints_f64, const int *count, const unsigned char *vis, int B, int V,
+                         int P, int J, int H, int W, double image_w, double image_h, double sigma, int Cp, void *out_cl,
+                         bool half, void *stream) {
+    if (!joints || !count || !out_cl) return FVP_ERR_NULL;
     RenderArgs a;
+    const int st = render_args(B, V, P, J, H, W, image_w, image_h, sigma, Cp, out_cl, half, &a);
+    if (st != FVP_OK) return st;
     a.joints = joints;
     a.count = count;
     a.vis = vis;
-    a.out = out_cl;
-    a.stride_x = image_w / (double)W;  // feat_stride = image_size / heatmap_size
-    a.stride_y = image_h / (double)H;
-    a.sigma = sigma;
     a.joints_f64 = joints_f64 != 0;
-    a.P = P;
-    a.J = J;
-    a.H = H;
-    a.W = W;
-    a.tiles_x = (W + kTileW - 1) / kTileW;
-    a.bands = (H + kBandH - 1) / kBandH;
-    const long long blocks = (long long)B * V * a.bands;
-    if (blocks > 0x7fffffffLL) return FVP_ERR_SHAPE;
-    const size_t lds = (size_t)P * J * (sizeof(double2) + sizeof(RenderRec) + sizeof(unsigned short)) +
-                       (size_t)P * sizeof(RenderPerson);
-    const dim3 grid((unsigned)blocks), block(kRenderThreads);
+    const size_t lds = render_lds_bytes(P, J);
+    const dim3 grid((unsigned)((long long)B * V * a.bands)), block(kRenderThreads);
     if (Cp == 16 && !half)
         hipLaunchKernelGGL((render_keypoints_kernel<16, 4>), grid, block, lds, (hipStream_t)stream, a);
     else if (!half)
@@ -307,4 +502,39 @@ extern "C" int fvp_render_keypoints_f16(const void *joints, int joints_f64, cons
                                         void *stream) {
     return fvp::render_launch(joints, joints_f64, count, vis, B, V, P, J, H, W, image_w, image_h, sigma, Cp,
                               out_cl_f16, true, stream);
+}
+
+extern "C" int fvp_project_poses(const double *joints3d, const unsigned char *vis3d, const int *count, int B, int P,
+                                 int J, const double *cams64, const int *cam_index, int S, int V,
+                                 const double *resize_t64, double ori_w, double ori_h, double image_w, double image_h,
+                                 double *joints2d, unsigned char *vis2d, void *stream) {
+    if (!joints2d || !vis2d) return FVP_ERR_NULL;
+    fvp::PoseArgs a;
+    const int st = fvp::pose_args(joints3d, vis3d, count, B, P, J, cams64, cam_index, S, V, resize_t64, ori_w, ori_h,
+                                  image_w, image_h, joints2d, vis2d, &a);
+    if (st != FVP_OK) return st;
+    const long long total = (long long)B * V * P * J;
+    const long long blocks = (total + fvp::kRenderThreads - 1) / fvp::kRenderThreads;
+    if (blocks > 0x7fffffffLL) return FVP_ERR_SHAPE;
+    hipLaunchKernelGGL(fvp::project_poses_kernel, dim3((unsigned)blocks), dim3(fvp::kRenderThreads), 0,
+                       (hipStream_t)stream, a, P * J, J, total);
+    return (int)hipGetLastError();
+}
+
+extern "C" int fvp_render_poses3d(const double *joints3d, const unsigned char *vis3d, const int *count, int B, int P,
+                                  int J, const double *cams64, const int *cam_index, int S, int V,
+                                  const double *resize_t64, double ori_w, double ori_h, double image_w, double image_h,
+                                  int H, int W, double sigma, int Cp, float *out_cl, double *joints2d,
+                                  unsigned char *vis2d, void *stream) {
+    return fvp::render_poses_launch(joints3d, vis3d, count, B, P, J, cams64, cam_index, S, V, resize_t64, ori_w, ori_h,
+                                    image_w, image_h, H, W, sigma, Cp, out_cl, joints2d, vis2d, false, stream);
+}
+
+extern "C" int fvp_render_poses3d_f16(const double *joints3d, const unsigned char *vis3d, const int *count, int B,
+                                      int P, int J, const double *cams64, const int *cam_index, int S, int V,
+                                      const double *resize_t64, double ori_w, double ori_h, double image_w,
+                                      double image_h, int H, int W, double sigma, int Cp, void *out_cl_f16,
+                                      double *joints2d, unsigned char *vis2d, void *stream) {
+    return fvp::render_poses_launch(joints3d, vis3d, count, B, P, J, cams64, cam_index, S, V, resize_t64, ori_w, ori_h,
+                                    image_w, image_h, H, W, sigma, Cp, out_cl_f16, joints2d, vis2d, true, stream);
 }

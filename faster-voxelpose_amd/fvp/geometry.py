@@ -55,6 +55,20 @@ def pack_cameras(cameras, seq) -> np.ndarray:
     return np.stack([pack_camera(c) for c in camera_list(cameras, seq)])
 
 
+def pack_cameras64(cameras, seq) -> np.ndarray:
+    """The cameras of ``seq`` as float64 [V, CAM_STRIDE] records in pack_camera's field
+    order, the dicts' float64 values as they are (no fp32 rounding): what the dataset's own
+    float64 projection reads (cameras.py:20-27 ``unfold_camera_param_cpu``), for the 'gt'
+    heatmap source (fvp.heatmaps.render_poses3d)."""
+    cams = camera_list(cameras, seq)
+    out = np.zeros((len(cams), CAM_STRIDE), dtype=np.float64)
+    for v, cam in enumerate(cams):
+        for lo, hi, value in ((0, 9, cam["R"]), (9, 12, cam["T"]), (12, 14, [cam["fx"], cam["fy"]]),
+                              (14, 16, [cam["cx"], cam["cy"]]), (16, 19, cam["k"]), (19, 21, cam["p"])):
+            out[v, lo:hi] = np.asarray(value, dtype=np.float64).reshape(hi - lo)
+    return out
+
+
 # ---------------------------------------------------------------------------
 # resize transform (cv2-free)
 # ---------------------------------------------------------------------------

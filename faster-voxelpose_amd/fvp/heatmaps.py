@@ -230,9 +230,9 @@ def render_keypoints(joints: torch.Tensor, count: torch.Tensor, vis: torch.Tenso
             bit for bit ``render_keypoints(...).half()`` without the cast pass
 
     A person with a non-finite coordinate is skipped (the reference raises).
-    Out of scope: the ``'gt'`` source (3-D joints projected through the cameras
-    first: project on the host and call this with ``vis``) and the
-    training-time random augmentation."""
+    The ``'gt'`` source (3-D joints projected through the cameras first) is
+    :func:`render_poses3d`, which projects and paints in one launch.  Out of
+    scope: the training-time random augmentation."""
     from . import ops
 
     if dtype not in (None, torch.float32, torch.float16):
@@ -268,3 +268,172 @@ def render_keypoints(joints: torch.Tensor, count: torch.Tensor, vis: torch.Tenso
     op = ops.render_keypoints_f16 if dtype == torch.float16 else ops.render_keypoints
     t = op(joints, count, vis, float(img_w), float(img_h), int(H), int(W), float(sigma))
     return ChannelsLastHeatmaps(t, J)
+
+
+def pack_poses3d(joints_3d, joints_3d_vis=None, max_people: int | None = None):
+    """One frame's 3-D ground truth as the reference dataset holds it
+    (``meta['joints_3d']`` / ``meta['joints_3d_vis']``, JointsDataset.py:107-117)
+    -- people as ``[J, >= 3]`` arrays (x, y, z in mm) and their visibility as
+    ``[J]`` arrays, or as ``[J, 3]`` arrays as Panoptic stores it -- as padded host
+    tensors for :func:`render_poses3d`: ``joints3d`` [P, J, 3] fp64, ``vis3d``
+    [P, J] uint8 and ``count``, a 0-d int32 tensor, with P = ``max_people`` or
+    the number of people (at least 1).  The default collate stacks the three
+    into [B, P, J, 3], [B, P, J] and [B].
+
+    A joint is visible where its flag is > 0 (JointsDataset.py:243); of a
+    ``[J, 3]`` array column 0 is read (the three columns repeat one flag, and the
+    reference's painter cannot read a row of three).  ``joints_3d_vis=None``:
+    every joint visible.  Padded rows are zero and never read; the all-zero
+    people meta['joints_3d'] is padded with may be passed too (their flags are
+    0, so they paint nothing, as in the reference)."""
+    import numpy as np
+
+    people = [np.asarray(p, dtype=np.float64) for p in joints_3d]
+    if not people and not (isinstance(joints_3d, np.ndarray) and joints_3d.ndim == 3):
+        raise _lib.FvpError("fvp: pack_poses3d: no person (the joint count is unknown)")
+    J = people[0].shape[0] if people else joints_3d.shape[1]
+    for p in people:
+        if p.ndim != 2 or p.shape[1] < 3 or p.shape[0] != J:
+            raise _lib.FvpError(f"fvp: pack_poses3d: each person is [J, >= 3] with one J, got {p.shape}")
+    P = max(len(people), 1) if max_people is None else int(max_people)
+    if len(people) > P:
+        raise _lib.FvpError(f"fvp: pack_poses3d: {len(people)} people, max_people = {P}")
+    joints = np.zeros((P, J, 3), dtype=np.float64)
+    vis = np.zeros((P, J), dtype=np.uint8)
+    for n, p in enumerate(people):
+        joints[n] = p[:, :3]
+    if joints_3d_vis is None:
+        vis[:len(people)] = 1
+    else:
+        flags = [np.asarray(f) for f in joints_3d_vis]
+        if len(flags) != len(people):
+            raise _lib.FvpError(f"fvp: pack_poses3d: {len(people)} people but {len(flags)} visibility arrays")
+        for n, f in enumerate(flags):
+            if f.shape not in ((J,), (J, 3)):
+                raise _lib.FvpError(f"fvp: pack_poses3d: visibility is [J] or [J, 3] with J = {J}, got {f.shape}")
+            vis[n] = (f if f.ndim == 1 else f[:, 0]) > 0
+    return torch.from_numpy(joints), torch.from_numpy(vis), torch.tensor(len(people), dtype=torch.int32)
+
+
+def _pose_call(name, joints3d, vis3d, count, cams, resize_transform, cam_index, ori_image_size, image_size):
+    """The validation render_poses3d and project_poses share; returns the operands as the ops take them."""
+    from . import ops
+
+    if not isinstance(joints3d, torch.Tensor) or joints3d.dim() != 4 or joints3d.shape[3] != 3 \
+            or joints3d.dtype != torch.float64:
+        raise _lib.FvpError(f"fvp: {name} takes joints3d fp64 [B,P,J,3], got "
+                            f"{tuple(getattr(joints3d, 'shape', ()))} {getattr(joints3d, 'dtype', type(joints3d))}")
+    B, P, J, _ = joints3d.shape
+    if J > 32 or P > 32 or J < 1 or P < 1:
+        raise _lib.FvpError(f"fvp: {name}: {P} people x {J} joints (1..32 each)")
+    if not isinstance(count, torch.Tensor) or tuple(count.shape) != (B,) or count.dtype != torch.int32:
+        raise _lib.FvpError(f"fvp: {name} takes count int32 [B] = {(B,)}, got "
+                            f"{tuple(getattr(count, 'shape', ()))} {getattr(count, 'dtype', type(count))}")
+    if vis3d is not None:
+        if not isinstance(vis3d, torch.Tensor) or tuple(vis3d.shape) != (B, P, J) \
+                or vis3d.dtype not in (torch.uint8, torch.bool):
+            raise _lib.FvpError(f"fvp: {name} takes vis3d uint8 / bool [B,P,J] = {(B, P, J)}, got "
+                                f"{tuple(getattr(vis3d, 'shape', ()))} {getattr(vis3d, 'dtype', type(vis3d))}")
+        if vis3d.dtype == torch.bool:
+            vis3d = vis3d.view(torch.uint8)
+    if not isinstance(cams, torch.Tensor) or cams.dim() not in (2, 3) or cams.shape[-1] != ops.CAM_STRIDE \
+            or cams.dtype != torch.float64 or cams.numel() == 0:
+        raise _lib.FvpError(f"fvp: {name} takes cams fp64 [V,{ops.CAM_STRIDE}] or [S,V,{ops.CAM_STRIDE}] "
+                            f"(geometry.pack_cameras64), got {tuple(getattr(cams, 'shape', ()))} "
+                            f"{getattr(cams, 'dtype', type(cams))}")
+    if cams.dim() == 2:
+        cams = cams.unsqueeze(0)
+    if not isinstance(resize_transform, torch.Tensor) or tuple(resize_transform.shape) != (2, 3) \
+            or resize_transform.dtype != torch.float64:
+        raise _lib.FvpError(f"fvp: {name} takes resize_transform fp64 [2,3], got "
+                            f"{tuple(getattr(resize_transform, 'shape', ()))} "
+                            f"{getattr(resize_transform, 'dtype', type(resize_transform))}")
+    if cam_index is not None:
+        if not isinstance(cam_index, torch.Tensor):
+            cam_index = torch.as_tensor(cam_index, dtype=torch.int32)
+        if tuple(cam_index.shape) != (B,) or cam_index.dtype != torch.int32:
+            raise _lib.FvpError(f"fvp: {name} takes cam_index int32 [B] = {(B,)}, got {tuple(cam_index.shape)} "
+                                f"{cam_index.dtype}")
+        if cam_index.device.type == "cpu":  # a host index is checked here; a device one is a precondition
+            if B and (int(cam_index.min()) < 0 or int(cam_index.max()) >= cams.shape[0]):
+                raise _lib.FvpError(f"fvp: {name}: cam_index must lie in 0..{cams.shape[0] - 1}, got "
+                                    f"{cam_index.tolist()}")
+            cam_index = cam_index.to(joints3d.device)
+    for what, t in (("joints3d", joints3d), ("vis3d", vis3d), ("count", count), ("cams", cams),
+                    ("resize_transform", resize_transform), ("cam_index", cam_index)):
+        if t is None:
+            continue
+        if t.device.type != "cuda" or t.device != joints3d.device:
+            raise _lib.FvpError(f"fvp: {name}: {what} must be on a HIP device (one for all operands), got {t.device}")
+        if not t.is_contiguous():
+            raise _lib.FvpError(f"fvp: {name}: {what} must be contiguous")
+    (ori_w, ori_h), (img_w, img_h) = ori_image_size, image_size
+    if not (ori_w > 0 and ori_h > 0 and img_w > 0 and img_h > 0):
+        raise _lib.FvpError(f"fvp: {name}: original image {ori_image_size}, image {image_size}")
+    ops.forward_only(joints3d, cams, resize_transform)
+    return joints3d, vis3d, count, cams, cam_index, resize_transform, float(ori_w), float(ori_h), float(img_w), \
+        float(img_h)
+
+
+def project_poses(joints3d: torch.Tensor, vis3d: torch.Tensor | None, count: torch.Tensor, cams: torch.Tensor,
+                  resize_transform: torch.Tensor, *, ori_image_size, image_size, cam_index=None):
+    """The 2-D ground truth of the ``'gt'`` heatmap source on the device, in one
+    launch (fvp_project_poses): ``project_pose_cpu`` (lib/utils/cameras.py:58-84),
+    the original-image test, ``affine_transform`` (lib/utils/transforms.py:53-56)
+    and the resized-image test of JointsDataset.py:231-254, for every view of
+    every frame.  Operands as :func:`render_poses3d`.  Returns ``(joints2d, vis2d)``:
+    [B, V, P, J, 2] fp64 image pixels after the resize transform and [B, V, P, J]
+    uint8, bit for bit the reference's float64 values; rows at or beyond
+    ``count`` are zero.  ``render_keypoints(joints2d, count[:, None].expand(B,
+    V).contiguous(), vis2d, ...)`` then equals ``render_poses3d``."""
+    from . import ops
+
+    return ops.project_poses(*_pose_call("project_poses", joints3d, vis3d, count, cams, resize_transform, cam_index,
+                                         ori_image_size, image_size))
+
+
+def render_poses3d(joints3d: torch.Tensor, vis3d: torch.Tensor | None, count: torch.Tensor, cams: torch.Tensor,
+                   resize_transform: torch.Tensor, *, ori_image_size, image_size, heatmap_size, sigma: float,
+                   dtype: torch.dtype | None = None, cam_index=None, return_keypoints: bool = False):
+    """Input heatmaps painted from 3-D ground-truth poses on the device,
+    channels-last, in one launch (fvp_render_poses3d): the ``'gt'`` branch of
+    JointsDataset.__getitem__ (lib/dataset/JointsDataset.py:221-259) --
+    ``TRAIN_HEATMAP_SRC: 'gt'`` of configs/shelf/jln64.yaml and
+    configs/campus/jln64.yaml, and the upper-bound ablation at test time -- with
+    ``data_augmentation = False``.  The launch projects every person into every
+    view in float64 in the reference's operation order, applies its two
+    visibility tests and paints as :func:`render_keypoints` does, so the result
+    is bit for bit ``render_keypoints(*project_poses(...))``.
+
+    joints3d  [B, P, J, 3] fp64 on a HIP device: meta['joints_3d'] (mm), see pack_poses3d
+    vis3d     [B, P, J] uint8 or bool, or None (all visible): meta['joints_3d_vis'] > 0
+    count     [B] int32: people of each frame (rows at or beyond it are never read)
+    cams      [V, 24] or [S, V, 24] fp64: geometry.pack_cameras64 of one or S sequences
+    resize_transform  [2, 3] fp64: the dataset's resize_transform (geometry.resize_transform)
+    ori_image_size, image_size, heatmap_size  (W, H);  sigma: NETWORK.SIGMA
+    dtype     None / torch.float32, or torch.float16 (fvp_render_poses3d_f16: bit for bit
+              the fp32 result's ``.half()``)
+    cam_index [B] int32, optional: the camera set of each frame, so that one batch can mix
+              sequences.  A host tensor or list is range-checked and uploaded; a device
+              tensor must hold values in 0..S-1.
+    return_keypoints  also return (joints2d, vis2d) as project_poses does, written by
+              the same launch
+
+    Every joint of a person enters the human scale, visible or not; only visible
+    joints are painted.  A person with a non-finite 2-D coordinate is skipped, a
+    point behind a camera is not special-cased (as in the reference), and a frame
+    without people is a frame of zeros (the reference raises).  Out of scope: the
+    training-time random augmentation."""
+    from . import ops
+
+    if dtype not in (None, torch.float32, torch.float16):
+        raise _lib.FvpError(f"fvp: render_poses3d: dtype must be None, torch.float32 or torch.float16, got {dtype}")
+    args = _pose_call("render_poses3d", joints3d, vis3d, count, cams, resize_transform, cam_index, ori_image_size,
+                      image_size)
+    W, H = heatmap_size
+    if int(W) != W or int(H) != H or W < 1 or H < 1 or not sigma > 0:
+        raise _lib.FvpError(f"fvp: render_poses3d: heatmap {heatmap_size}, sigma {sigma}")
+    op = ops.render_poses3d_f16 if dtype == torch.float16 else ops.render_poses3d
+    t, joints2d, vis2d = op(*args, int(H), int(W), float(sigma), bool(return_keypoints))
+    cl = ChannelsLastHeatmaps(t, joints3d.shape[2])
+    return (cl, joints2d, vis2d) if return_keypoints else cl

@@ -19,6 +19,7 @@ import torch
 
 from . import _lib
 from ._lib import GridSpec, ImageSpec, PersonSpec
+from .geometry import CAM_STRIDE
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -851,6 +852,146 @@ def render_keypoints_f16(joints: torch.Tensor, count: torch.Tensor, vis: Optiona
 def _(joints, count, vis, image_w, image_h, H, W, sigma):
     B, V, _, J, _ = joints.shape
     return joints.new_empty((B, V, H, W, render_cp(J)), dtype=torch.float16)
+
+
+def _pose_operands(joints3d, vis3d, count, cams, cam_index, resize_t, device) -> tuple[int, int, int, int, int]:
+    """(B, P, J, S, V) of the 'gt' operands after the checks the three pose entry points share:
+    dtypes, shapes, contiguity, one HIP device (fvp.heatmaps.render_poses3d says what each is)."""
+    ok = (joints3d.dim() == 4 and joints3d.shape[3] == 3 and joints3d.dtype == torch.float64
+          and cams.dim() == 3 and cams.shape[2] == CAM_STRIDE and cams.dtype == torch.float64
+          and tuple(resize_t.shape) == (2, 3) and resize_t.dtype == torch.float64 and count.dtype == torch.int32
+          and tuple(count.shape) == tuple(joints3d.shape[:1]))
+    if ok and vis3d is not None:
+        ok = vis3d.dtype == torch.uint8 and tuple(vis3d.shape) == tuple(joints3d.shape[:3])
+    if ok and cam_index is not None:
+        ok = cam_index.dtype == torch.int32 and tuple(cam_index.shape) == tuple(joints3d.shape[:1])
+    if not ok:
+        raise _lib.FvpError(
+            f"fvp: pose operands: joints3d fp64 [B,P,J,3] {tuple(joints3d.shape)} {joints3d.dtype}, vis3d uint8 "
+            f"[B,P,J] {None if vis3d is None else (tuple(vis3d.shape), vis3d.dtype)}, count int32 [B] "
+            f"{tuple(count.shape)} {count.dtype}, cams fp64 [S,V,{CAM_STRIDE}] {tuple(cams.shape)} {cams.dtype}, "
+            f"cam_index int32 [B] {None if cam_index is None else (tuple(cam_index.shape), cam_index.dtype)}, "
+            f"resize_transform fp64 [2,3] {tuple(resize_t.shape)} {resize_t.dtype}")
+    for t in (joints3d, vis3d, count, cams, cam_index, resize_t):
+        if t is None:
+            continue
+        if t.device.type != "cuda" or t.device != device:
+            raise _lib.FvpError(f"fvp: pose operands must share one HIP device, got {t.device}")
+        if not t.is_contiguous():
+            raise _lib.FvpError("fvp: pose operands must be contiguous")
+    B, P, J, _ = joints3d.shape
+    return B, P, J, cams.shape[0], cams.shape[1]
+
+
+def _pose_outputs(joints2d, vis2d, shape, device) -> None:
+    for t, dtype, want in ((joints2d, torch.float64, shape + (2,)), (vis2d, torch.uint8, shape)):
+        if t is not None and (t.dtype != dtype or tuple(t.shape) != want or not t.is_contiguous()
+                              or t.device != device):
+            raise _lib.FvpError(f"fvp: pose outputs: expected contiguous {dtype} {want} on {device}, got "
+                                f"{tuple(t.shape)} {t.dtype} on {t.device}")
+
+
+@_custom_op("fvp::project_poses", mutates_args=(), device_types="cuda")
+def project_poses(joints3d: torch.Tensor, vis3d: Optional[torch.Tensor], count: torch.Tensor, cams: torch.Tensor,
+                  cam_index: Optional[torch.Tensor], resize_t: torch.Tensor, ori_w: float, ori_h: float,
+                  image_w: float, image_h: float) -> tuple[torch.Tensor, torch.Tensor]:
+    """joints3d [B,P,J,3] fp64, vis3d [B,P,J] uint8 or None, count [B] int32, cams [S,V,24] fp64,
+    cam_index [B] int32 or None, resize_t [2,3] fp64 -> (joints2d [B,V,P,J,2] fp64, vis2d [B,V,P,J]
+    uint8): the 'gt' projection and its two visibility tests (fvp_project_poses, one launch)."""
+    B, P, J, S, V = _pose_operands(joints3d, vis3d, count, cams, cam_index, resize_t, joints3d.device)
+    joints2d = torch.empty((B, V, P, J, 2), dtype=torch.float64, device=joints3d.device)
+    vis2d = torch.empty((B, V, P, J), dtype=torch.uint8, device=joints3d.device)
+    if joints2d.numel():
+        _lib.call("fvp_project_poses", _ptr(joints3d), _ptr(vis3d), _ptr(count), B, P, J, _ptr(cams), _ptr(cam_index),
+                  S, V, _ptr(resize_t), float(ori_w), float(ori_h), float(image_w), float(image_h), _ptr(joints2d),
+                  _ptr(vis2d), _stream(joints2d))
+    return joints2d, vis2d
+
+
+@project_poses.register_fake
+def _(joints3d, vis3d, count, cams, cam_index, resize_t, ori_w, ori_h, image_w, image_h):
+    B, P, J, _ = joints3d.shape
+    V = cams.shape[1]
+    return (joints3d.new_empty((B, V, P, J, 2), dtype=torch.float64),
+            joints3d.new_empty((B, V, P, J), dtype=torch.uint8))
+
+
+def render_poses3d_into(joints3d: torch.Tensor, vis3d: Optional[torch.Tensor], count: torch.Tensor,
+                        cams: torch.Tensor, cam_index: Optional[torch.Tensor], resize_t: torch.Tensor, ori_w: float,
+                        ori_h: float, image_w: float, image_h: float, sigma: float, out: torch.Tensor,
+                        joints2d: Optional[torch.Tensor] = None,
+                        vis2d: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fvp_render_poses3d into `out` [B,V,H,W,Cp] fp32, or fvp_render_poses3d_f16 into an fp16 `out`
+    (every element is overwritten), and the 2-D keypoints / flags into `joints2d` [B,V,P,J,2] fp64 /
+    `vis2d` [B,V,P,J] uint8 where given (every element overwritten; rows at or beyond count with 0)."""
+    B, P, J, S, V = _pose_operands(joints3d, vis3d, count, cams, cam_index, resize_t, out.device)
+    if (out.dim() != 5 or out.dtype not in (torch.float32, torch.float16) or not out.is_contiguous()
+            or tuple(out.shape[:2]) != (B, V)):
+        raise _lib.FvpError(f"fvp: render_poses3d: out must be contiguous fp32 / fp16 [{B},{V},H,W,Cp], got "
+                            f"{tuple(out.shape)} {out.dtype}")
+    _pose_outputs(joints2d, vis2d, (B, V, P, J), out.device)
+    H, W, cp = out.shape[2], out.shape[3], out.shape[4]
+    if out.numel():
+        _lib.call(_f16("fvp_render_poses3d", out), _ptr(joints3d), _ptr(vis3d), _ptr(count), B, P, J, _ptr(cams),
+                  _ptr(cam_index), S, V, _ptr(resize_t), float(ori_w), float(ori_h), float(image_w), float(image_h),
+                  H, W, float(sigma), cp, _ptr(out), _ptr(joints2d), _ptr(vis2d), _stream(out))
+    return out
+
+
+def _render_poses3d(dtype, joints3d, vis3d, count, cams, cam_index, resize_t, ori_w, ori_h, image_w, image_h, H, W,
+                    sigma, keypoints):
+    if joints3d.dim() != 4 or cams.dim() != 3:  # (render_poses3d_into checks the rest)
+        raise _lib.FvpError(f"fvp: render_poses3d takes joints3d [B,P,J,3] and cams [S,V,{CAM_STRIDE}], got "
+                            f"{tuple(joints3d.shape)}, {tuple(cams.shape)}")
+    B, P, J, _ = joints3d.shape
+    V, dev = cams.shape[1], joints3d.device
+    out = torch.empty((B, V, H, W, render_cp(J)), dtype=dtype, device=dev)
+    joints2d = torch.empty((B, V, P, J, 2) if keypoints else (0,), dtype=torch.float64, device=dev)
+    vis2d = torch.empty((B, V, P, J) if keypoints else (0,), dtype=torch.uint8, device=dev)
+    render_poses3d_into(joints3d, vis3d, count, cams, cam_index, resize_t, ori_w, ori_h, image_w, image_h, sigma, out,
+                        joints2d if keypoints else None, vis2d if keypoints else None)
+    return out, joints2d, vis2d
+
+
+def _render_poses3d_fake(dtype, joints3d, cams, H, W, keypoints):
+    B, P, J, _ = joints3d.shape
+    V = cams.shape[1]
+    return (joints3d.new_empty((B, V, H, W, render_cp(J)), dtype=dtype),
+            joints3d.new_empty((B, V, P, J, 2) if keypoints else (0,), dtype=torch.float64),
+            joints3d.new_empty((B, V, P, J) if keypoints else (0,), dtype=torch.uint8))
+
+
+@_custom_op("fvp::render_poses3d", mutates_args=(), device_types="cuda")
+def render_poses3d(joints3d: torch.Tensor, vis3d: Optional[torch.Tensor], count: torch.Tensor, cams: torch.Tensor,
+                   cam_index: Optional[torch.Tensor], resize_t: torch.Tensor, ori_w: float, ori_h: float,
+                   image_w: float, image_h: float, H: int, W: int, sigma: float,
+                   keypoints: bool) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The operands of project_poses -> channels-last 'gt' heatmaps [B,V,H,W,16*ceil(J/16)] fp32
+    (fvp_render_poses3d, one launch), plus joints2d [B,V,P,J,2] and vis2d [B,V,P,J] written by the
+    same launch when `keypoints` (else two empty tensors)."""
+    return _render_poses3d(torch.float32, joints3d, vis3d, count, cams, cam_index, resize_t, ori_w, ori_h, image_w,
+                           image_h, H, W, sigma, keypoints)
+
+
+@render_poses3d.register_fake
+def _(joints3d, vis3d, count, cams, cam_index, resize_t, ori_w, ori_h, image_w, image_h, H, W, sigma, keypoints):
+    return _render_poses3d_fake(torch.float32, joints3d, cams, H, W, keypoints)
+
+
+@_custom_op("fvp::render_poses3d_f16", mutates_args=(), device_types="cuda")
+def render_poses3d_f16(joints3d: torch.Tensor, vis3d: Optional[torch.Tensor], count: torch.Tensor,
+                       cams: torch.Tensor, cam_index: Optional[torch.Tensor], resize_t: torch.Tensor, ori_w: float,
+                       ori_h: float, image_w: float, image_h: float, H: int, W: int, sigma: float,
+                       keypoints: bool) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """render_poses3d writing fp16 channels-last heatmaps directly (fvp_render_poses3d_f16, one
+    launch): bit for bit render_poses3d(...)[0].half()."""
+    return _render_poses3d(torch.float16, joints3d, vis3d, count, cams, cam_index, resize_t, ori_w, ori_h, image_w,
+                           image_h, H, W, sigma, keypoints)
+
+
+@render_poses3d_f16.register_fake
+def _(joints3d, vis3d, count, cams, cam_index, resize_t, ori_w, ori_h, image_w, image_h, H, W, sigma, keypoints):
+    return _render_poses3d_fake(torch.float16, joints3d, cams, H, W, keypoints)
 
 
 def mask_nonzero(mask: torch.Tensor) -> torch.Tensor:

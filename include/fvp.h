@@ -756,6 +756,68 @@ int fvp_render_keypoints_f16(const void *joints, int joints_f64, const int *coun
                              int V, int P, int J, int H, int W, double image_w, double image_h, double sigma, int Cp,
                              void *out_cl_f16, void *stream);
 
+/* The 'gt' heatmap source (DATASET.TRAIN_HEATMAP_SRC / TEST_HEATMAP_SRC 'gt'):
+ * 3-D ground-truth joints projected into every view, replacing the per-view,
+ * per-person host loop of JointsDataset.__getitem__ (lib/dataset/JointsDataset.py:
+ * 231-254: project_pose_cpu, lib/utils/cameras.py:58-84, then affine_transform
+ * per joint, lib/utils/transforms.py:53-56).  fp64, one rounded operation per
+ * line unless an fma is written, in the order numpy evaluates the reference
+ * (its 3x3 matmul and 2x3 dot accumulate with fma, first term a plain product):
+ *   d    = X - T
+ *   xc_r = fma(R[r][2], d2, fma(R[r][1], d1, R[r][0] * d0))              r = 0, 1, 2
+ *   y0   = xc_0 / (xc_2 + 1e-5);  y1 = xc_1 / (xc_2 + 1e-5);  r = y0*y0 + y1*y1
+ *   dd   = ((1 + k0*r) + (k1*r)*r) + ((k2*r)*r)*r
+ *   u    = (y0*dd + ((2*p0)*y0)*y1) + p1*(r + (2*y0)*y0)
+ *   w    = (y1*dd + ((2*p1)*y0)*y1) + p0*(r + (2*y1)*y1)
+ *   px   = fx*u + cx;  py = fy*w + cy
+ *   vis  = vis3d > 0 && 0 <= px <= ori_w - 1 && 0 <= py <= ori_h - 1
+ *   qx   = fma(t00, px, t01*py) + t02;  qy = fma(t10, px, t11*py) + t12
+ *   vis  = 0 if min(qx, qy) < 0 || qx >= image_w || qy >= image_h
+ * A point behind the camera is not special-cased (the reference does not), and
+ * NaN compares false everywhere as in numpy, so a NaN pixel is invisible.
+ *   joints3d   device fp64 [B][P][J][3] (meta['joints_3d']), shared by the views
+ *   vis3d      device uint8 [B][P][J] (meta['joints_3d_vis'] > 0) or NULL: all visible
+ *   count      device int32 [B]: people of the frame, 0 <= count <= P; input rows at
+ *              or beyond it are never read
+ *   cams64     device fp64 [S][V][FVP_CAM_STRIDE], the field order of the fp32 record
+ *   cam_index  device int32 [B] or NULL (every frame uses set 0): the camera set of
+ *              each frame, 0 <= cam_index < S (a precondition; values outside are
+ *              pinned into the range)
+ *   resize_t64 device fp64 [2][3]: the dataset's resize_transform
+ *   ori_w, ori_h   the original image size;  image_w, image_h  NETWORK.IMAGE_SIZE
+ *   joints2d   device fp64 [B][V][P][J][2]: (qx, qy), image pixels after the transform
+ *   vis2d      device uint8 [B][V][P][J]: 1 = visible
+ * Every element of both outputs is written; rows at or beyond count hold 0.
+ * FVP_ERR_NULL: a missing pointer (vis3d and cam_index may be NULL); FVP_ERR_SHAPE:
+ * J or P outside 1..32, V outside 1..FVP_MAX_VIEWS, S < 1, B < 1, a size that is
+ * not positive and finite.  Asynchronous, no allocation, no workspace. */
+int fvp_project_poses(const double *joints3d, const unsigned char *vis3d, const int *count, int B, int P, int J,
+                      const double *cams64, const int *cam_index, int S, int V, const double *resize_t64, double ori_w,
+                      double ori_h, double image_w, double image_h, double *joints2d, unsigned char *vis2d,
+                      void *stream);
+/* The 'gt' input heatmaps in one launch (JointsDataset.py:221-259): the projection
+ * above, then the painter of fvp_render_keypoints (JointsDataset.py:368-447) on
+ * (qx, qy) and vis -- every joint of a person, visible or not, enters the human
+ * scale, only visible joints are painted, a person with a non-finite 2-D
+ * coordinate is skipped, and a frame without people is a frame of zeros (the
+ * reference raises).  Bit for bit fvp_project_poses followed by
+ * fvp_render_keypoints with the frame's count for each of its views.
+ *   out_cl     device [B][V][H][W][Cp] fp32, as fvp_render_keypoints writes it
+ *   joints2d, vis2d   as above, each optional (NULL: not written)
+ * Host checks: those of fvp_project_poses and of fvp_render_keypoints (Cp % 16 == 0,
+ * J <= Cp <= 32; H, W, sigma > 0). */
+int fvp_render_poses3d(const double *joints3d, const unsigned char *vis3d, const int *count, int B, int P, int J,
+                       const double *cams64, const int *cam_index, int S, int V, const double *resize_t64,
+                       double ori_w, double ori_h, double image_w, double image_h, int H, int W, double sigma, int Cp,
+                       float *out_cl, double *joints2d, unsigned char *vis2d, void *stream);
+/* The same (JointsDataset.py:221-259) writing fp16 channels-last heatmaps as
+ * fvp_render_keypoints_f16 does: out_cl_f16 device [B][V][H][W][Cp] fp16, 16-B
+ * aligned; bit for bit fvp_render_poses3d followed by Tensor.half(). */
+int fvp_render_poses3d_f16(const double *joints3d, const unsigned char *vis3d, const int *count, int B, int P, int J,
+                           const double *cams64, const int *cam_index, int S, int V, const double *resize_t64,
+                           double ori_w, double ori_h, double image_w, double image_h, int H, int W, double sigma,
+                           int Cp, void *out_cl_f16, double *joints2d, unsigned char *vis2d, void *stream);
+
 /* PoseResNet's final_layer (lib/models/resnet.py:122-128 with FINAL_CONV_KERNEL: 1,
  * applied at :199: a 1x1 convolution Cin -> J plus bias) writing fp16
  * channels-last heatmap rows directly -- the input of fvp_voxelize_cl_f16 --
