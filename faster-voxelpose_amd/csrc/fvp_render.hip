@@ -40,6 +40,16 @@
 // numpy evaluates them -- and keeps the visibility byte in LDS.  Everything after
 // that loop is the one body, so the result equals fvp_project_poses followed by
 // fvp_render_keypoints bit for bit.
+//
+// Augmented heatmaps (fvp_render_keypoints_aug, fvp_render_poses3d_aug): the same
+// kernel with AUG = true paints generate_input_heatmap with data_augmentation =
+// True (JointsDataset.py:413-432).  The random draws are the caller's: one record
+// per (frame, view, person, joint) holds the factor the patch is multiplied by and
+// the rectangle of the patch that is zeroed.  The thread that builds a joint's
+// window keeps the record in the 16 bytes of q[] it has just read for the last
+// time, so an AUG block takes the LDS of a plain one; the pixel loop multiplies
+// g by the factor outside the rectangle, contributes nothing inside it, and the
+// maximum is clamped at 1 before the store (a factor can exceed 1).
 #include <math.h>
 
 #include <type_traits>
@@ -97,6 +107,27 @@ struct RenderPoseArgs : RenderArgs {
     PoseArgs pose;
 };
 
+// The augmentation records, one per (frame, view, person, joint) as vis is laid out.
+struct AugArgs {
+    const float *scale;  // [B][V][P][J]
+    const short *rect;   // [B][V][P][J][4]: rows r0, r1, columns c0, c1 of the patch
+};
+
+template <class Base>
+struct WithAug : Base {
+    AugArgs aug;
+};
+
+// A listed joint's augmentation in LDS: the factor, and the zeroed rectangle [r0, r1) x [c0, c1) in
+// patch coordinates (negative values pinned to 0) with the patch's centre pc, so that the pixel at
+// (dx, dy) from the Gaussian's centre is the patch's (dx + pc, dy + pc).
+struct AugRec {
+    float scale;
+    int pc;
+    short r0, r1, c0, c1;
+};
+static_assert(sizeof(AugRec) == sizeof(double2), "an AugRec takes the place of its joint's q");
+
 // One joint through one camera: project_point_cpu (cameras.py:58-84), the original-image test
 // (JointsDataset.py:238-244), affine_transform (transforms.py:53-56) and the resized-image test
 // (JointsDataset.py:249-251).  fp64, one rounded operation per operator, fma() only where numpy's
@@ -153,9 +184,13 @@ struct RenderAcc<8> {
 
 // JPL: joints (channels) per lane = per 16-B store: 4 fp32 or 8 fp16.
 // POSE: the records start from 3-D joints (a.pose) instead of a.joints / a.vis.
-template <int CP, int JPL, bool POSE = false>
-__global__ __launch_bounds__(kRenderThreads) void render_keypoints_kernel(
-    const std::conditional_t<POSE, RenderPoseArgs, RenderArgs> a) {
+// AUG: every painted joint is scaled and cut by its record of a.aug, and the output is clamped at 1.
+template <bool POSE, bool AUG>
+using RenderKernelArgs = std::conditional_t<AUG, WithAug<std::conditional_t<POSE, RenderPoseArgs, RenderArgs>>,
+                                            std::conditional_t<POSE, RenderPoseArgs, RenderArgs>>;
+
+template <int CP, int JPL, bool POSE = false, bool AUG = false>
+__global__ __launch_bounds__(kRenderThreads) void render_keypoints_kernel(const RenderKernelArgs<POSE, AUG> a) {
     constexpr int QP = CP / JPL;              // channel groups (one 16-B piece) per pixel
     constexpr int PPP = kRenderThreads / QP;  // pixels per pass
     constexpr int PASSES = kTileW * kBandH / PPP;
@@ -286,6 +321,18 @@ __global__ __launch_bounds__(kRenderThreads) void render_keypoints_kernel(
         }
         if (rec.x0 < rec.x1 && rec.y0 < ty0 + kBandH && rec.y1 > ty0) {
             recs[r] = rec;
+            if constexpr (AUG) {  // over q[r], which only this thread read since the last barrier
+                const long long e = (long long)bv * nrec + r;
+                const short *rc = a.aug.rect + e * 4;
+                AugRec ar;
+                ar.scale = a.aug.scale[e];
+                ar.pc = pr.c0;
+                ar.r0 = rc[0] < 0 ? (short)0 : rc[0];
+                ar.r1 = rc[1] < 0 ? (short)0 : rc[1];
+                ar.c0 = rc[2] < 0 ? (short)0 : rc[2];
+                ar.c1 = rc[3] < 0 ? (short)0 : rc[3];
+                reinterpret_cast<AugRec *>(q)[r] = ar;
+            }
             band[atomicAdd(&band_n, 1)] = (unsigned short)r;
         }
     }
@@ -320,8 +367,15 @@ __global__ __launch_bounds__(kRenderThreads) void render_keypoints_kernel(
                 const int id = kept[set][grp][i];
                 const RenderRec rec = recs[id >> SH];
                 if (x >= rec.x0 && x < rec.x1 && y >= rec.y0 && y < rec.y1) {
-                    const float dx = (float)(x - rec.cx), dy = (float)(y - rec.cy);
-                    const float g = expf(-((dx * dx + dy * dy) * rec.inv));
+                    const int dxi = x - rec.cx, dyi = y - rec.cy;
+                    const float dx = (float)dxi, dy = (float)dyi;
+                    float g = expf(-((dx * dx + dy * dy) * rec.inv));
+                    if constexpr (AUG) {  // nothing inside the rectangle; a NaN or negative product loses to acc >= 0
+                        const AugRec ar = reinterpret_cast<const AugRec *>(q)[id >> SH];
+                        const int px = dxi + ar.pc, py = dyi + ar.pc;
+                        const bool cut = px >= ar.c0 && px < ar.c1 && py >= ar.r0 && py < ar.r1;
+                        g = cut ? 0.0f : g * ar.scale;
+                    }
                     const int k = id & (JPL - 1);
                     acc.x = k == 0 ? fmaxf(acc.x, g) : acc.x;
                     acc.y = k == 1 ? fmaxf(acc.y, g) : acc.y;
@@ -334,6 +388,12 @@ __global__ __launch_bounds__(kRenderThreads) void render_keypoints_kernel(
                         va.hi.w = k == 7 ? fmaxf(va.hi.w, g) : va.hi.w;
                     }
                 }
+            }
+            if constexpr (AUG) {  // np.clip(target, 0, 1): a factor above 1 lifts the centre pixel over it
+                acc = make_float4(fminf(acc.x, 1.0f), fminf(acc.y, 1.0f), fminf(acc.z, 1.0f), fminf(acc.w, 1.0f));
+                if constexpr (JPL == 8)
+                    va.hi = make_float4(fminf(va.hi.x, 1.0f), fminf(va.hi.y, 1.0f), fminf(va.hi.z, 1.0f),
+                                        fminf(va.hi.w, 1.0f));
             }
             if (x < W && y < H) {
                 OutT *o = obase + (y * W + x) * CP;
@@ -432,12 +492,30 @@ static size_t render_lds_bytes(int P, int J) {
            (size_t)P * sizeof(RenderPerson);
 }
 
-// Host checks and the launch shared by fvp_render_poses3d (half = false) and fvp_render_poses3d_f16.
+// One of the 16 instantiations: Cp 16 or 32, fp32 (4 joints per lane) or fp16 (8) output.
+template <bool POSE, bool AUG>
+static int render_dispatch(int Cp, bool half, dim3 grid, size_t lds, void *stream,
+                           const RenderKernelArgs<POSE, AUG> &a) {
+    const dim3 block(kRenderThreads);
+    if (Cp == 16 && !half)
+        hipLaunchKernelGGL((render_keypoints_kernel<16, 4, POSE, AUG>), grid, block, lds, (hipStream_t)stream, a);
+    else if (!half)
+        hipLaunchKernelGGL((render_keypoints_kernel<32, 4, POSE, AUG>), grid, block, lds, (hipStream_t)stream, a);
+    else if (Cp == 16)
+        hipLaunchKernelGGL((render_keypoints_kernel<16, 8, POSE, AUG>), grid, block, lds, (hipStream_t)stream, a);
+    else
+        hipLaunchKernelGGL((render_keypoints_kernel<32, 8, POSE, AUG>), grid, block, lds, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+}
+
+// Host checks and the launch shared by fvp_render_poses3d (half = false), fvp_render_poses3d_f16 and
+// fvp_render_poses3d_aug (aug_scale and aug_rect given).
 static int render_poses_launch(const double *joints3d, const unsigned char *vis3d, const int *count, int B, int P,
                                int J, const double *cams64, const int *cam_index, int S, int V,
                                const double *resize_t64, double ori_w, double ori_h, double image_w, double image_h,
                                int H, int W, double sigma, int Cp, void *out_cl, double *joints2d,
-                               unsigned char *vis2d, bool half, void *stream) {
+                               unsigned char *vis2d, bool half, void *stream, const float *aug_scale = nullptr,
+                               const short *aug_rect = nullptr) {
     if (!out_cl) return FVP_ERR_NULL;
     RenderPoseArgs a;
     int st = pose_args(joints3d, vis3d, count, B, P, J, cams64, cam_index, S, V, resize_t64, ori_w, ori_h, image_w,
@@ -450,22 +528,22 @@ static int render_poses_launch(const double *joints3d, const unsigned char *vis3
     a.vis = nullptr;
     a.joints_f64 = 1;
     const size_t lds = render_lds_bytes(P, J) + (size_t)P * J;  // + the 2-D visibility bytes
-    const dim3 grid((unsigned)((long long)B * V * a.bands)), block(kRenderThreads);
-    if (Cp == 16 && !half)
-        hipLaunchKernelGGL((render_keypoints_kernel<16, 4, true>), grid, block, lds, (hipStream_t)stream, a);
-    else if (!half)
-        hipLaunchKernelGGL((render_keypoints_kernel<32, 4, true>), grid, block, lds, (hipStream_t)stream, a);
-    else if (Cp == 16)
-        hipLaunchKernelGGL((render_keypoints_kernel<16, 8, true>), grid, block, lds, (hipStream_t)stream, a);
-    else
-        hipLaunchKernelGGL((render_keypoints_kernel<32, 8, true>), grid, block, lds, (hipStream_t)stream, a);
-    return (int)hipGetLastError();
+    const dim3 grid((unsigned)((long long)B * V * a.bands));
+    if (aug_scale) {
+        WithAug<RenderPoseArgs> g;
+        static_cast<RenderPoseArgs &>(g) = a;
+        g.aug.scale = aug_scale;
+        g.aug.rect = aug_rect;
+        return render_dispatch<true, true>(Cp, half, grid, lds, stream, g);
+    }
+    return render_dispatch<true, false>(Cp, half, grid, lds, stream, a);
 }
 
-// Host checks and the launch shared by the fp32 (half = false) and fp16 entry points.
+// Host checks and the launch shared by the fp32 (half = false), fp16 and augmented (aug_scale and
+// aug_rect given) entry points.
 static int render_launch(const void *joints, int joints_f64, const int *count, const unsigned char *vis, int B, int V,
                          int P, int J, int H, int W, double image_w, double image_h, double sigma, int Cp, void *out_cl,
-                         bool half, void *stream) {
+                         bool half, void *stream, const float *aug_scale = nullptr, const short *aug_rect = nullptr) {
     if (!joints || !count || !out_cl) return FVP_ERR_NULL;
     RenderArgs a;
     const int st = render_args(B, V, P, J, H, W, image_w, image_h, sigma, Cp, out_cl, half, &a);
@@ -475,16 +553,15 @@ static int render_launch(const void *joints, int joints_f64, const int *count, c
     a.vis = vis;
     a.joints_f64 = joints_f64 != 0;
     const size_t lds = render_lds_bytes(P, J);
-    const dim3 grid((unsigned)((long long)B * V * a.bands)), block(kRenderThreads);
-    if (Cp == 16 && !half)
-        hipLaunchKernelGGL((render_keypoints_kernel<16, 4>), grid, block, lds, (hipStream_t)stream, a);
-    else if (!half)
-        hipLaunchKernelGGL((render_keypoints_kernel<32, 4>), grid, block, lds, (hipStream_t)stream, a);
-    else if (Cp == 16)
-        hipLaunchKernelGGL((render_keypoints_kernel<16, 8>), grid, block, lds, (hipStream_t)stream, a);
-    else
-        hipLaunchKernelGGL((render_keypoints_kernel<32, 8>), grid, block, lds, (hipStream_t)stream, a);
-    return (int)hipGetLastError();
+    const dim3 grid((unsigned)((long long)B * V * a.bands));
+    if (aug_scale) {
+        WithAug<RenderArgs> g;
+        static_cast<RenderArgs &>(g) = a;
+        g.aug.scale = aug_scale;
+        g.aug.rect = aug_rect;
+        return render_dispatch<false, true>(Cp, half, grid, lds, stream, g);
+    }
+    return render_dispatch<false, false>(Cp, half, grid, lds, stream, a);
 }
 
 }  // namespace fvp
@@ -537,4 +614,25 @@ extern "C" int fvp_render_poses3d_f16(const double *joints3d, const unsigned cha
                                       double *joints2d, unsigned char *vis2d, void *stream) {
     return fvp::render_poses_launch(joints3d, vis3d, count, B, P, J, cams64, cam_index, S, V, resize_t64, ori_w, ori_h,
                                     image_w, image_h, H, W, sigma, Cp, out_cl_f16, joints2d, vis2d, true, stream);
+}
+
+extern "C" int fvp_render_keypoints_aug(const void *joints, int joints_f64, const int *count,
+                                        const unsigned char *vis, const float *aug_scale, const short *aug_rect,
+                                        int B, int V, int P, int J, int H, int W, double image_w, double image_h,
+                                        double sigma, int Cp, void *out_cl, int out_half, void *stream) {
+    if (!aug_scale || !aug_rect) return FVP_ERR_NULL;
+    return fvp::render_launch(joints, joints_f64, count, vis, B, V, P, J, H, W, image_w, image_h, sigma, Cp, out_cl,
+                              out_half != 0, stream, aug_scale, aug_rect);
+}
+
+extern "C" int fvp_render_poses3d_aug(const double *joints3d, const unsigned char *vis3d, const int *count, int B,
+                                      int P, int J, const double *cams64, const int *cam_index, int S, int V,
+                                      const double *resize_t64, double ori_w, double ori_h, double image_w,
+                                      double image_h, const float *aug_scale, const short *aug_rect, int H, int W,
+                                      double sigma, int Cp, void *out_cl, int out_half, double *joints2d,
+                                      unsigned char *vis2d, void *stream) {
+    if (!aug_scale || !aug_rect) return FVP_ERR_NULL;
+    return fvp::render_poses_launch(joints3d, vis3d, count, B, P, J, cams64, cam_index, S, V, resize_t64, ori_w, ori_h,
+                                    image_w, image_h, H, W, sigma, Cp, out_cl, joints2d, vis2d, out_half != 0, stream,
+                                    aug_scale, aug_rect);
 }

@@ -163,6 +163,13 @@ SIGNATURES = {
     "fvp_render_poses3d_f16": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
                                c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_int,
                                c_int, ctypes.c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    "fvp_render_keypoints_aug": [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                 c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_int, c_void_p,
+                                 c_int, c_void_p],
+    "fvp_render_poses3d_aug": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
+                               c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_void_p,
+                               c_void_p, c_int, c_int, ctypes.c_double, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                               c_void_p],
     "fvp_conv1x1_cl_f16": [c_void_p, ctypes.c_longlong, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int,
                            c_void_p, c_void_p],
 }

@@ -10,6 +10,8 @@ through the reference's interfaces attached to the planar tensor it equals
 """
 from __future__ import annotations
 
+from typing import NamedTuple
+
 import torch
 
 from . import _lib
@@ -210,8 +212,134 @@ def pack_keypoints(all_preds, max_people: int | None = None):
     return torch.from_numpy(joints), torch.from_numpy(count)
 
 
+class Augmentation(NamedTuple):
+    """The random draws of generate_input_heatmap with ``data_augmentation = True``, one record per
+    joint (:func:`draw_augmentation`): ``scale`` [..., P, J] fp32, the factor a joint's patch is
+    multiplied by, and ``rect`` [..., P, J, 4] int16 = (r0, r1, c0, c1), the rows and columns of
+    the patch that are zeroed.  (1, empty rectangle) is the identity."""
+    scale: torch.Tensor
+    rect: torch.Tensor
+
+
+def _host_array(t, dtype=None):
+    import numpy as np
+
+    if isinstance(t, torch.Tensor):
+        t = t.detach().cpu().numpy()
+    return np.asarray(t) if dtype is None else np.asarray(t, dtype=dtype)
+
+
+def _trunc(v) -> int:
+    """Python's int(), pinned to +-2^30 as the kernel pins it."""
+    return int(min(max(float(v), -1073741824.0), 1073741824.0))
+
+
+def draw_augmentation(joints, count, vis=None, *, image_size, heatmap_size, sigma: float, py_rng=None,
+                      np_rng=None) -> Augmentation:
+    """The random draws JointsDataset.generate_input_heatmap makes with
+    ``data_augmentation = True`` (lib/dataset/JointsDataset.py:413-432) for one
+    frame, as the records ``render_keypoints(..., augment=)`` and
+    ``render_poses3d(..., augment=)`` take: host tensors ``scale`` [V, P, J] fp32
+    and ``rect`` [V, P, J, 4] int16.  Use it beside :func:`pack_keypoints` in the
+    dataset's ``__getitem__``; the default collate stacks the frames.
+
+    joints  [V, P, J, 2] host tensor or array, image pixels after the resize transform
+            (pack_keypoints; for ``'gt'``, the keypoints of project_poses copied to the
+            host, or the dataset's own)
+    count   [V] people of each view;  vis [V, P, J] or None: 0 = joint not painted
+    py_rng, np_rng  a ``random.Random`` and a ``np.random.RandomState``; default: the
+            global ``random`` and ``np.random`` streams the reference reads
+
+    The streams are consumed exactly as the reference consumes them: views, then
+    people, then joints; a joint that is invisible, off the map (the painter's
+    skip test) or of a person with a non-finite coordinate draws nothing and gets
+    the identity record; every other joint -- one whose window ends at ``br == 0``
+    and paints nothing included -- draws ``random()`` (< 0.6: ``randn(1)`` follows,
+    scale = 0.9 + 0.03 randn), ``random()`` again for the second factor (joints 7,
+    8: x0.5 below 0.1; joints 9, 10: x0.2 below 0.1; others: x0.5 below 0.05) and
+    four ``uniform`` values for the rectangle.  The window is restated in float64
+    in the reference's operation order, as the kernel computes it."""
+    import math
+    import random
+
+    import numpy as np
+
+    rnd = (py_rng if py_rng is not None else random).random
+    npr = np_rng if np_rng is not None else np.random
+    jn = _host_array(joints)
+    if jn.ndim != 4 or jn.shape[3] != 2:
+        raise _lib.FvpError(f"fvp: draw_augmentation takes joints [V,P,J,2], got {jn.shape}")
+    V, P, J, _ = jn.shape
+    cn = _host_array(count).reshape(-1)
+    if cn.shape[0] != V:
+        raise _lib.FvpError(f"fvp: draw_augmentation takes count [V] = {(V,)}, got {cn.shape}")
+    vn = None if vis is None else _host_array(vis)
+    if vn is not None and vn.shape != (V, P, J):
+        raise _lib.FvpError(f"fvp: draw_augmentation takes vis [V,P,J] = {(V, P, J)}, got {vn.shape}")
+    (img_w, img_h), (W, H) = image_size, heatmap_size
+    W, H = int(W), int(H)
+    stride = (float(img_w) / float(W), float(img_h) / float(H))
+    scale = np.ones((V, P, J), np.float32)
+    rect = np.zeros((V, P, J, 4), np.int16)
+    for v in range(V):
+        for p in range(min(max(int(cn[v]), 0), P)):
+            q = jn[v, p].astype(np.float64) / np.asarray(stride, np.float64)
+            if not np.isfinite(q).all():
+                continue
+            ext = np.maximum(q[:, 1].max() - q[:, 1].min(), q[:, 0].max() - q[:, 0].min())
+            human = 2 * np.clip(ext * ext, 1.0 / 4 * 96 ** 2, 4 * 96 ** 2)
+            tmp = float(np.float64(sigma) * np.sqrt(human / (96.0 * 96.0)) * 3)
+            for j in range(J):
+                if vn is not None and vn[v, p, j] == 0:
+                    continue
+                mu_x, mu_y = _trunc(q[j, 0]), _trunc(q[j, 1])
+                ul = (_trunc(mu_x - tmp), _trunc(mu_y - tmp))
+                br = (_trunc(mu_x + tmp + 1), _trunc(mu_y + tmp + 1))
+                if ul[0] >= W or ul[1] >= H or br[0] < 0 or br[1] < 0:
+                    continue
+                s = 0.9 + float(npr.randn(1)[0]) * 0.03 if rnd() < 0.6 else 1.0
+                second = rnd()
+                if j in (7, 8):
+                    s = s * 0.5 if second < 0.1 else s
+                elif j in (9, 10):
+                    s = s * 0.2 if second < 0.1 else s
+                else:
+                    s = s * 0.5 if second < 0.05 else s
+                r0 = int(npr.uniform(0, H - 1))
+                c0 = int(npr.uniform(0, W - 1))
+                r1 = int(min(r0 + npr.uniform(H / 4, H * 0.75), H))
+                c1 = int(min(c0 + npr.uniform(W / 4, W * 0.75), W))
+                scale[v, p, j] = s
+                rect[v, p, j] = [min(max(x, 0), 32767) for x in (r0, r1, c0, c1)]
+    return Augmentation(torch.from_numpy(scale), torch.from_numpy(rect))
+
+
+def _augment_records(name: str, augment, shape: tuple, device):
+    """(scale, rect) of an ``augment=`` argument as the ops take them: checked, contiguous, on `device`
+    (host records, as the collate stacks them, are uploaded)."""
+    try:
+        scale, rect = augment
+    except (TypeError, ValueError):
+        scale = rect = None
+    if not isinstance(scale, torch.Tensor) or not isinstance(rect, torch.Tensor) \
+            or tuple(scale.shape) != shape or tuple(rect.shape) != shape + (4,) \
+            or scale.dtype != torch.float32 or rect.dtype != torch.int16:
+        got = [(tuple(t.shape), t.dtype) if isinstance(t, torch.Tensor) else type(t) for t in (scale, rect)]
+        raise _lib.FvpError(f"fvp: {name}: augment is (scale fp32 [B,V,P,J] = {shape}, rect int16 [B,V,P,J,4]) "
+                            f"(heatmaps.draw_augmentation, stacked), got {got}")
+    out = []
+    for t in (scale, rect):
+        if t.device.type == "cpu":
+            t = t.to(device)
+        elif t.device != device:
+            raise _lib.FvpError(f"fvp: {name}: augment must be on the host or on {device}, got {t.device}")
+        out.append(t.contiguous())
+    return out
+
+
 def render_keypoints(joints: torch.Tensor, count: torch.Tensor, vis: torch.Tensor | None = None, *, image_size,
-                     heatmap_size, sigma: float, dtype: torch.dtype | None = None) -> ChannelsLastHeatmaps:
+                     heatmap_size, sigma: float, dtype: torch.dtype | None = None,
+                     augment=None) -> ChannelsLastHeatmaps:
     """Input heatmaps painted from 2-D keypoints on the device, channels-last,
     in one launch (fvp_render_keypoints): JointsDataset.generate_input_heatmap
     (lib/dataset/JointsDataset.py:368-447) with ``data_augmentation = False``,
@@ -228,11 +356,16 @@ def render_keypoints(joints: torch.Tensor, count: torch.Tensor, vis: torch.Tenso
     dtype   None / torch.float32, or torch.float16: the fp16 channels-last layout the
             fp16 gathers read, written by the same launch (fvp_render_keypoints_f16) --
             bit for bit ``render_keypoints(...).half()`` without the cast pass
+    augment None, or the :class:`Augmentation` of :func:`draw_augmentation` stacked to
+            scale [B, V, P, J] fp32 and rect [B, V, P, J, 4] int16 (on the host or on the
+            operands' device): ``data_augmentation = True`` (JointsDataset.py:413-432, the
+            setting of the Shelf and Campus configs) in the same launch
+            (fvp_render_keypoints_aug) -- each painted joint is multiplied by its scale and
+            zeroed inside its rectangle, and the result is clamped at 1
 
     A person with a non-finite coordinate is skipped (the reference raises).
     The ``'gt'`` source (3-D joints projected through the cameras first) is
-    :func:`render_poses3d`, which projects and paints in one launch.  Out of
-    scope: the training-time random augmentation."""
+    :func:`render_poses3d`, which projects and paints in one launch."""
     from . import ops
 
     if dtype not in (None, torch.float32, torch.float16):
@@ -265,6 +398,11 @@ def render_keypoints(joints: torch.Tensor, count: torch.Tensor, vis: torch.Tenso
     if int(W) != W or int(H) != H or W < 1 or H < 1 or not (img_w > 0 and img_h > 0 and sigma > 0):
         raise _lib.FvpError(f"fvp: render_keypoints: image {image_size}, heatmap {heatmap_size}, sigma {sigma}")
     ops.forward_only(joints)
+    if augment is not None:
+        scale, rect = _augment_records("render_keypoints", augment, (B, V, P, J), joints.device)
+        t = ops.render_keypoints_aug(joints, count, vis, scale, rect, float(img_w), float(img_h), int(H), int(W),
+                                     float(sigma), dtype == torch.float16)
+        return ChannelsLastHeatmaps(t, J)
     op = ops.render_keypoints_f16 if dtype == torch.float16 else ops.render_keypoints
     t = op(joints, count, vis, float(img_w), float(img_h), int(H), int(W), float(sigma))
     return ChannelsLastHeatmaps(t, J)
@@ -394,16 +532,18 @@ def project_poses(joints3d: torch.Tensor, vis3d: torch.Tensor | None, count: tor
 
 def render_poses3d(joints3d: torch.Tensor, vis3d: torch.Tensor | None, count: torch.Tensor, cams: torch.Tensor,
                    resize_transform: torch.Tensor, *, ori_image_size, image_size, heatmap_size, sigma: float,
-                   dtype: torch.dtype | None = None, cam_index=None, return_keypoints: bool = False):
+                   dtype: torch.dtype | None = None, cam_index=None, return_keypoints: bool = False,
+                   augment=None):
     """Input heatmaps painted from 3-D ground-truth poses on the device,
     channels-last, in one launch (fvp_render_poses3d): the ``'gt'`` branch of
     JointsDataset.__getitem__ (lib/dataset/JointsDataset.py:221-259) --
     ``TRAIN_HEATMAP_SRC: 'gt'`` of configs/shelf/jln64.yaml and
     configs/campus/jln64.yaml, and the upper-bound ablation at test time -- with
-    ``data_augmentation = False``.  The launch projects every person into every
-    view in float64 in the reference's operation order, applies its two
-    visibility tests and paints as :func:`render_keypoints` does, so the result
-    is bit for bit ``render_keypoints(*project_poses(...))``.
+    ``data_augmentation = False``, or ``True`` when ``augment`` is given.  The
+    launch projects every person into every view in float64 in the reference's
+    operation order, applies its two visibility tests and paints as
+    :func:`render_keypoints` does, so the result is bit for bit
+    ``render_keypoints(*project_poses(...))``.
 
     joints3d  [B, P, J, 3] fp64 on a HIP device: meta['joints_3d'] (mm), see pack_poses3d
     vis3d     [B, P, J] uint8 or bool, or None (all visible): meta['joints_3d_vis'] > 0
@@ -418,12 +558,16 @@ def render_poses3d(joints3d: torch.Tensor, vis3d: torch.Tensor | None, count: to
               tensor must hold values in 0..S-1.
     return_keypoints  also return (joints2d, vis2d) as project_poses does, written by
               the same launch
+    augment   None, or the :class:`Augmentation` records as :func:`render_keypoints` takes
+              them, [B, V, P, J] and [B, V, P, J, 4] (fvp_render_poses3d_aug).  Draw them with
+              :func:`draw_augmentation` from the frame's 2-D keypoints and flags --
+              ``project_poses(...)`` copied to the host, or the dataset's own -- and the
+              result is bit for bit ``render_keypoints(*project_poses(...), augment=augment)``
 
     Every joint of a person enters the human scale, visible or not; only visible
     joints are painted.  A person with a non-finite 2-D coordinate is skipped, a
     point behind a camera is not special-cased (as in the reference), and a frame
-    without people is a frame of zeros (the reference raises).  Out of scope: the
-    training-time random augmentation."""
+    without people is a frame of zeros (the reference raises)."""
     from . import ops
 
     if dtype not in (None, torch.float32, torch.float16):
@@ -433,7 +577,13 @@ def render_poses3d(joints3d: torch.Tensor, vis3d: torch.Tensor | None, count: to
     W, H = heatmap_size
     if int(W) != W or int(H) != H or W < 1 or H < 1 or not sigma > 0:
         raise _lib.FvpError(f"fvp: render_poses3d: heatmap {heatmap_size}, sigma {sigma}")
-    op = ops.render_poses3d_f16 if dtype == torch.float16 else ops.render_poses3d
-    t, joints2d, vis2d = op(*args, int(H), int(W), float(sigma), bool(return_keypoints))
+    if augment is not None:
+        B, P, J, _ = joints3d.shape
+        scale, rect = _augment_records("render_poses3d", augment, (B, args[3].shape[1], P, J), joints3d.device)
+        t, joints2d, vis2d = ops.render_poses3d_aug(*args[:6], scale, rect, *args[6:], int(H), int(W), float(sigma),
+                                                    bool(return_keypoints), dtype == torch.float16)
+    else:
+        op = ops.render_poses3d_f16 if dtype == torch.float16 else ops.render_poses3d
+        t, joints2d, vis2d = op(*args, int(H), int(W), float(sigma), bool(return_keypoints))
     cl = ChannelsLastHeatmaps(t, joints3d.shape[2])
     return (cl, joints2d, vis2d) if return_keypoints else cl

@@ -994,6 +994,98 @@ def _(joints3d, vis3d, count, cams, cam_index, resize_t, ori_w, ori_h, image_w, 
     return _render_poses3d_fake(torch.float16, joints3d, cams, H, W, keypoints)
 
 
+def _aug_operands(aug_scale: torch.Tensor, aug_rect: torch.Tensor, shape: tuple, device) -> None:
+    """The augmentation records of the *_aug renders: fp32 [B,V,P,J] and int16 [B,V,P,J,4], contiguous,
+    on the device of the other operands."""
+    if (aug_scale.dtype != torch.float32 or tuple(aug_scale.shape) != shape or aug_rect.dtype != torch.int16
+            or tuple(aug_rect.shape) != shape + (4,)):
+        raise _lib.FvpError(f"fvp: augmentation records: scale fp32 {shape} and rect int16 {shape + (4,)}, got "
+                            f"{tuple(aug_scale.shape)} {aug_scale.dtype}, {tuple(aug_rect.shape)} {aug_rect.dtype}")
+    for t in (aug_scale, aug_rect):
+        if t.device.type != "cuda" or t.device != device:
+            raise _lib.FvpError(f"fvp: augmentation records must be on the operands' HIP device, got {t.device}")
+        if not t.is_contiguous():
+            raise _lib.FvpError("fvp: augmentation records must be contiguous")
+
+
+def render_keypoints_aug_into(joints: torch.Tensor, count: torch.Tensor, vis: Optional[torch.Tensor],
+                              aug_scale: torch.Tensor, aug_rect: torch.Tensor, image_w: float, image_h: float,
+                              sigma: float, out: torch.Tensor) -> torch.Tensor:
+    """fvp_render_keypoints_aug into `out` [B,V,H,W,Cp] fp32 or fp16 (every element is overwritten):
+    render_keypoints_into with one augmentation record per joint (fvp.heatmaps.draw_augmentation)."""
+    B, V, P, J, _ = joints.shape
+    H, W, cp = out.shape[2], out.shape[3], out.shape[4]
+    if (joints.dtype not in (torch.float32, torch.float64) or not joints.is_contiguous() or joints.shape[4] != 2
+            or count.dtype != torch.int32 or not count.is_contiguous() or tuple(count.shape) != (B, V)
+            or out.dtype not in (torch.float32, torch.float16) or not out.is_contiguous()
+            or tuple(out.shape[:2]) != (B, V)
+            or (vis is not None and (vis.dtype != torch.uint8 or not vis.is_contiguous()
+                                     or tuple(vis.shape) != (B, V, P, J)))):
+        raise _lib.FvpError(f"fvp: render_keypoints operands: joints {tuple(joints.shape)} {joints.dtype}, count "
+                            f"{tuple(count.shape)} {count.dtype}, out {tuple(out.shape)} {out.dtype}")
+    for t in (joints, count, vis):
+        if t is not None and (t.device.type != "cuda" or t.device != out.device):
+            raise _lib.FvpError(f"fvp: render_keypoints operands must share one HIP device, got {t.device}")
+    _aug_operands(aug_scale, aug_rect, (B, V, P, J), out.device)
+    if out.numel():
+        _lib.call("fvp_render_keypoints_aug", _ptr(joints), int(joints.dtype == torch.float64), _ptr(count),
+                  _ptr(vis), _ptr(aug_scale), _ptr(aug_rect), B, V, P, J, H, W, float(image_w), float(image_h),
+                  float(sigma), cp, _ptr(out), int(out.dtype == torch.float16), _stream(out))
+    return out
+
+
+@_custom_op("fvp::render_keypoints_aug", mutates_args=(), device_types="cuda")
+def render_keypoints_aug(joints: torch.Tensor, count: torch.Tensor, vis: Optional[torch.Tensor],
+                         aug_scale: torch.Tensor, aug_rect: torch.Tensor, image_w: float, image_h: float, H: int,
+                         W: int, sigma: float, half: bool) -> torch.Tensor:
+    """render_keypoints with data_augmentation = True: aug_scale [B,V,P,J] fp32 and aug_rect [B,V,P,J,4]
+    int16 scale and cut each painted joint, and the output is clamped at 1 (fvp_render_keypoints_aug,
+    one launch).  `half`: fp16 output, bit for bit the fp32 result's .half()."""
+    if joints.dim() != 5:
+        raise _lib.FvpError(f"fvp: render_keypoints joints must be [B,V,P,J,2], got {tuple(joints.shape)}")
+    B, V, _, J, _ = joints.shape
+    out = torch.empty((B, V, H, W, render_cp(J)), dtype=torch.float16 if half else torch.float32,
+                      device=joints.device)
+    return render_keypoints_aug_into(joints, count, vis, aug_scale, aug_rect, image_w, image_h, sigma, out)
+
+
+@render_keypoints_aug.register_fake
+def _(joints, count, vis, aug_scale, aug_rect, image_w, image_h, H, W, sigma, half):
+    B, V, _, J, _ = joints.shape
+    return joints.new_empty((B, V, H, W, render_cp(J)), dtype=torch.float16 if half else torch.float32)
+
+
+@_custom_op("fvp::render_poses3d_aug", mutates_args=(), device_types="cuda")
+def render_poses3d_aug(joints3d: torch.Tensor, vis3d: Optional[torch.Tensor], count: torch.Tensor,
+                       cams: torch.Tensor, cam_index: Optional[torch.Tensor], resize_t: torch.Tensor,
+                       aug_scale: torch.Tensor, aug_rect: torch.Tensor, ori_w: float, ori_h: float, image_w: float,
+                       image_h: float, H: int, W: int, sigma: float, keypoints: bool,
+                       half: bool) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """render_poses3d with data_augmentation = True (fvp_render_poses3d_aug, one launch): bit for bit
+    project_poses followed by render_keypoints_aug.  Records as render_keypoints_aug takes them."""
+    if joints3d.dim() != 4 or cams.dim() != 3:
+        raise _lib.FvpError(f"fvp: render_poses3d takes joints3d [B,P,J,3] and cams [S,V,{CAM_STRIDE}], got "
+                            f"{tuple(joints3d.shape)}, {tuple(cams.shape)}")
+    dev = joints3d.device
+    B, P, J, S, V = _pose_operands(joints3d, vis3d, count, cams, cam_index, resize_t, dev)
+    _aug_operands(aug_scale, aug_rect, (B, V, P, J), dev)
+    out = torch.empty((B, V, H, W, render_cp(J)), dtype=torch.float16 if half else torch.float32, device=dev)
+    joints2d = torch.empty((B, V, P, J, 2) if keypoints else (0,), dtype=torch.float64, device=dev)
+    vis2d = torch.empty((B, V, P, J) if keypoints else (0,), dtype=torch.uint8, device=dev)
+    if out.numel():
+        _lib.call("fvp_render_poses3d_aug", _ptr(joints3d), _ptr(vis3d), _ptr(count), B, P, J, _ptr(cams),
+                  _ptr(cam_index), S, V, _ptr(resize_t), float(ori_w), float(ori_h), float(image_w), float(image_h),
+                  _ptr(aug_scale), _ptr(aug_rect), H, W, float(sigma), render_cp(J), _ptr(out), int(half),
+                  _ptr(joints2d) if keypoints else None, _ptr(vis2d) if keypoints else None, _stream(out))
+    return out, joints2d, vis2d
+
+
+@render_poses3d_aug.register_fake
+def _(joints3d, vis3d, count, cams, cam_index, resize_t, aug_scale, aug_rect, ori_w, ori_h, image_w, image_h, H, W,
+      sigma, keypoints, half):
+    return _render_poses3d_fake(torch.float16 if half else torch.float32, joints3d, cams, H, W, keypoints)
+
+
 def mask_nonzero(mask: torch.Tensor) -> torch.Tensor:
     """``mask.nonzero()`` of a 2-D bool mask on the device in one launch (fvp_mask_nonzero): the
     [count, 2] int64 (row, col) pairs in row-major order.  Reading the count is the one host

@@ -818,6 +818,48 @@ int fvp_render_poses3d_f16(const double *joints3d, const unsigned char *vis3d, c
                            double ori_w, double ori_h, double image_w, double image_h, int H, int W, double sigma,
                            int Cp, void *out_cl_f16, double *joints2d, unsigned char *vis2d, void *stream);
 
+/* The same two painters with data_augmentation = True (JointsDataset.py:413-432;
+ * DATA_AUGMENTATION: true of configs/shelf/jln64.yaml and configs/campus/jln64.yaml,
+ * which JointsDataset reads for the training and the test set alike).  The
+ * reference draws, per painted joint -- one that is neither invisible nor skipped
+ * by the off-map test above -- a factor for its patch and a rectangle of the
+ * patch that is zeroed; here the caller draws them (fvp.heatmaps.draw_augmentation
+ * consumes Python's and numpy's streams in the reference's order) and hands over
+ * one record per (frame, view, person, joint):
+ *   aug_scale  device fp32 [B][V][P][J]: the patch is multiplied by it
+ *   aug_rect   device int16 [B][V][P][J][4] = (r0, r1, c0, c1): rows [r0, r1) and
+ *              columns [c0, c1) of the n x n patch (n = ceil(2 tmp + 1), row 0 and
+ *              column 0 at ul) are zeroed, as g[r0:r1, c0:c1] = 0
+ * A joint's pixel value becomes
+ *   0                                          inside the rectangle
+ *   (float)exp(...) * aug_scale  (one fp32 product)  elsewhere in its window
+ * a channel's pixel is the max over the people as before, then min(max, 1): the
+ * reference's np.clip(target, 0, 1), which a factor above 1 makes live.  The
+ * record (1.0f, empty rectangle) is the identity: the output then equals the
+ * plain painter's bit for bit.  Records of joints that are not painted, and of
+ * rows at or beyond count, are never read.
+ * Deviations: the rectangle is two half-open ranges intersected with the patch,
+ * empty when r0 >= r1 or c0 >= c1; values are read as 0..32767 with negative ones
+ * pinned to 0 (numpy would count a negative index from the patch's end; the
+ * reference never draws one).  A factor that is <= 0 or NaN paints nothing (the
+ * max starts at 0; the reference's factor is positive unless randn < -30).
+ *   out_cl     device [B][V][H][W][Cp] fp32 (out_half == 0), or fp16 and 16-B aligned
+ *              (out_half != 0): bit for bit the fp32 result followed by Tensor.half()
+ * The other arguments and the host checks are those of fvp_render_keypoints (_f16)
+ * and fvp_render_poses3d (_f16); FVP_ERR_NULL also for a missing aug_scale or
+ * aug_rect.  fvp_render_poses3d_aug equals fvp_project_poses followed by
+ * fvp_render_keypoints_aug bit for bit.  No workspace; the block's LDS is that of
+ * the plain painter (a listed joint's record replaces its q = joint / stride). */
+int fvp_render_keypoints_aug(const void *joints, int joints_f64, const int *count, const unsigned char *vis,
+                             const float *aug_scale, const short *aug_rect, int B, int V, int P, int J, int H, int W,
+                             double image_w, double image_h, double sigma, int Cp, void *out_cl, int out_half,
+                             void *stream);
+int fvp_render_poses3d_aug(const double *joints3d, const unsigned char *vis3d, const int *count, int B, int P, int J,
+                           const double *cams64, const int *cam_index, int S, int V, const double *resize_t64,
+                           double ori_w, double ori_h, double image_w, double image_h, const float *aug_scale,
+                           const short *aug_rect, int H, int W, double sigma, int Cp, void *out_cl, int out_half,
+                           double *joints2d, unsigned char *vis2d, void *stream);
+
 /* PoseResNet's final_layer (lib/models/resnet.py:122-128 with FINAL_CONV_KERNEL: 1,
  * applied at :199: a 1x1 convolution Cin -> J plus bias) writing fp16
  * channels-last heatmap rows directly -- the input of fvp_voxelize_cl_f16 --
