@@ -2468,6 +2468,7 @@ extern "C" int fvp_maxpool_pad_nhwc(const float *in, int N, int H, int W, int C,
     if (!in || !out) return FVP_ERR_NULL;
     if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 4 || K < 1 || S < 1 || P < 0 || 2 * P > K) return FVP_ERR_SHAPE;
     if (H + 2 * P < K || W + 2 * P < K) return FVP_ERR_SHAPE;
+    if (((uintptr_t)in | (uintptr_t)out) & 15) return FVP_ERR_SHAPE;  // 16-B loads and stores
     const int Ho = (H + 2 * P - K) / S + 1, Wo = (W + 2 * P - K) / S + 1;
     const long long total = (long long)N * Ho * Wo * (C / 4);
     if (K == 3 && S == 2 && P == 1 && (long long)N * Ho <= 65535 && (long long)H * W * (C / 4) < 0x7fffffffLL) {
@@ -2487,6 +2488,7 @@ extern "C" int fvp_maxpool_pad_nhwc_bf16(const void *in, int N, int H, int W, in
     if (!in || !out) return FVP_ERR_NULL;
     if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8 || K < 1 || S < 1 || P < 0 || 2 * P > K) return FVP_ERR_SHAPE;
     if (H + 2 * P < K || W + 2 * P < K) return FVP_ERR_SHAPE;
+    if (((uintptr_t)in | (uintptr_t)out) & 15) return FVP_ERR_SHAPE;  // 16-B loads and stores
     const int Ho = (H + 2 * P - K) / S + 1, Wo = (W + 2 * P - K) / S + 1;
     const long long total = (long long)N * Ho * Wo * (C / 8);
     hipLaunchKernelGGL(fvp::maxpool_pad_bf16_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
@@ -2500,6 +2502,7 @@ extern "C" int fvp_maxpool_nhwc_bf16(const void *in, int N, int H, int W, int C,
     if (!in || !out) return FVP_ERR_NULL;
     if (KH < 1 || KH > 2 || KW < 1 || KW > 2) return FVP_ERR_SHAPE;
     if (N <= 0 || H < KH || W < KW || C <= 0 || C % 8) return FVP_ERR_SHAPE;
+    if (((uintptr_t)in | (uintptr_t)out) & 15) return FVP_ERR_SHAPE;  // 16-B loads and stores
     const long long total = (long long)N * (H / KH) * (W / KW) * (C / 8);
     const dim3 g((unsigned)((total + 255) / 256)), b(256);
     hipStream_t st = (hipStream_t)stream;
@@ -2517,6 +2520,7 @@ extern "C" int fvp_maxpool_nhwc(const float *in, int N, int H, int W, int C, int
     if (!in || !out) return FVP_ERR_NULL;
     if (KH < 1 || KH > 2 || KW < 1 || KW > 2) return FVP_ERR_SHAPE;
     if (N <= 0 || H < KH || W < KW || C <= 0 || C % 4) return FVP_ERR_SHAPE;
+    if (((uintptr_t)in | (uintptr_t)out) & 15) return FVP_ERR_SHAPE;  // 16-B loads and stores
     const long long total = (long long)N * (H / KH) * (W / KW) * (C / 4);
     const dim3 g((unsigned)((total + 255) / 256)), b(256);
     hipStream_t st = (hipStream_t)stream;
@@ -2536,8 +2540,10 @@ extern "C" int fvp_nchw_to_nhwc(const float *in, int N, int C, int H, int W, int
     if (N <= 0 || C <= 0 || Cp < C || H <= 0 || W <= 0) return FVP_ERR_SHAPE;
     hipStream_t s = (hipStream_t)stream;
     // pitches of 4..32 channels (heatmaps: 16 * ceil(J / 16)): the voxelize layout
-    // pass, one float4 per thread, a wave writing a contiguous 1 KiB run
-    switch (Cp) {
+    // pass, one float4 per thread, a wave writing a contiguous 1 KiB run (16-B
+    // stores: an `out` that is not 16-B aligned takes the element kernel, as a
+    // misaligned `in` does in fvp_nhwc_to_nchw)
+    switch ((reinterpret_cast<uintptr_t>(out) & 15) ? 0 : Cp) {
         case 4: fvp::launch_layout<1, float>(in, N, 1, C, C, H, W, out, s); return (int)hipGetLastError();
         case 8: fvp::launch_layout<2, float>(in, N, 1, C, C, H, W, out, s); return (int)hipGetLastError();
         case 16: fvp::launch_layout<4, float>(in, N, 1, C, C, H, W, out, s); return (int)hipGetLastError();

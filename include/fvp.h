@@ -630,7 +630,9 @@ int fvp_up2_head_nchw(const float *in, int N, int H, int W, int Cpi, const float
 /* Output size of a geometry (host only): out_hw = {Ho, Wo}; FVP_ERR_SHAPE if invalid. */
 int fvp_conv2d_geom(int H, int W, int Cpi, int KH, int KW, int mode, int sy, int sx, int py, int px, int *out_hw);
 /* MaxPool2d(K, S, P) of NHWC activations (C % 4 == 0) with implicit -inf
- * padding, NaN-propagating (resnet.py:109: 3, 2, 1).  Ho = (H + 2P - K)/S + 1. */
+ * padding, NaN-propagating (resnet.py:109: 3, 2, 1).  Ho = (H + 2P - K)/S + 1.
+ * in and out 16-B aligned (16-B loads and stores), as for every pool below:
+ * FVP_ERR_SHAPE otherwise. */
 int fvp_maxpool_pad_nhwc(const float *in, int N, int H, int W, int C, int K, int S, int P, float *out, void *stream);
 /* The same on bf16 NHWC activations (C % 8 == 0; exact: the maximum is one
  * of the inputs) -- the bf16 backbone's max pool after its bf16 stem. */
@@ -704,7 +706,9 @@ int fvp_maxpool_nhwc_bf16(const void *in, int N, int H, int W, int C, int KH, in
 int fvp_weight_net(const float *features, int Nimg, int H, int W, const float *conv_w, const float *scale,
                    const float *shift, int C, const float *fc1_w, const float *fc1_b, int Hd, const float *fc2_w,
                    const float *fc2_b, float *out, void *stream);
-/* NCHW [N][C][H][W] <-> NHWC [N][H][W][Cp] (Cp >= C, padding channels zero). */
+/* NCHW [N][C][H][W] <-> NHWC [N][H][W][Cp] (Cp >= C, padding channels zero).
+ * Any float alignment: the 16-B kernels (Cp 4, 8, 16, 32 to NHWC; Cp % 4 == 0 and
+ * C <= 128 to NCHW) run only when the NHWC side is 16-B aligned. */
 int fvp_nchw_to_nhwc(const float *in, int N, int C, int H, int W, int Cp, float *out, void *stream);
 int fvp_nhwc_to_nchw(const float *in, int N, int C, int H, int W, int Cp, float *out, void *stream);
 /* Planar [N][C][H][W] fp32 (in_half = 0) or fp16 (1) -> channels-last fp16
