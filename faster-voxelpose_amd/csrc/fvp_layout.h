@@ -232,23 +232,34 @@ __global__ __launch_bounds__(256) void pairs_vec8_kernel(const _Float16 *__restr
 
 inline size_t pair_frame_bytes(int V, int H, int W) { return (size_t)V * H * (W + 1) * 64; }
 
+// Which kernel lays the pair table out (fvp_pair_layout_kind reports it): 8 entries a
+// thread wherever rows are 16-B aligned: C5, 4 frames per entry 98.2 -> 72.5 us, one
+// frame 20.4 -> 15.9 us (profiles/round4/pairs8/).  Otherwise row blocks for frame
+// groups (a 15 KB row per block leaves its load / store phases exposed at one frame:
+// 40.8 vs 20.8 us per entry), and the per-entry kernel for single frames, odd widths,
+// 2-B-aligned pointers (a C-ABI caller may pass any fp16 pointer; the row kernel loads
+// 4 B) and rows beyond 64 KiB of LDS.
+enum PairLayout { kPairsVec8 = 0, kPairsRows = 1, kPairsEntry = 2 };
+
+inline size_t pairs_rows_lds(int NF, int W) { return (size_t)NF * 16 * (W / 2 + 2) * 4; }
+
+inline PairLayout pair_layout_kind(int NF, int W, unsigned long long hm) {
+    if (W % 8 == 0 && (hm & 15ull) == 0) return kPairsVec8;
+    if (NF > 1 && (hm & 3ull) == 0 && W % 2 == 0 && pairs_rows_lds(NF, W) <= 64 * 1024) return kPairsRows;
+    return kPairsEntry;
+}
+
 // Launch the pair-table layout for nb frames (a multiple of NF).
 template <int NF>
 inline void launch_pairs(const _Float16 *hm, int nb, int V, int J, int H, int W, uint4 *tab, hipStream_t s) {
-    const size_t lds = (size_t)NF * 16 * (W / 2 + 2) * 4;
-    // 8 entries a thread wherever rows are 16-B aligned: C5, 4 frames per entry
-    // 98.2 -> 72.5 us, one frame 20.4 -> 15.9 us (profiles/round4/pairs8/).
-    // Otherwise row blocks for frame groups (a 15 KB row per block leaves its
-    // load / store phases exposed at one frame: 40.8 vs 20.8 us per entry), and
-    // the per-entry kernel for single frames, odd widths and 2-B-aligned pointers.
-    const bool aligned = ((unsigned long long)hm & 3ull) == 0;  // 4-B row loads (a C-ABI caller may pass any fp16 pointer)
-    if (W % 8 == 0 && ((unsigned long long)hm & 15ull) == 0) {
+    const PairLayout kind = pair_layout_kind(NF, W, (unsigned long long)hm);
+    if (kind == kPairsVec8) {
         const long long total = (long long)nb / NF * V * H * (W / 8) * NF * 4;
         hipLaunchKernelGGL((pairs_vec8_kernel<NF>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, hm, tab,
                            J, H, W, V, total);
-    } else if (NF > 1 && aligned && W % 2 == 0 && lds <= 64 * 1024) {
-        hipLaunchKernelGGL((pairs_rows_kernel<NF>), dim3((unsigned)((long long)nb / NF * V * H)), dim3(256), lds, s, hm,
-                           tab, J, H, W, V);
+    } else if (kind == kPairsRows) {
+        hipLaunchKernelGGL((pairs_rows_kernel<NF>), dim3((unsigned)((long long)nb / NF * V * H)), dim3(256),
+                           pairs_rows_lds(NF, W), s, hm, tab, J, H, W, V);
     } else {
         const long long total = (long long)nb * V * H * (W + 1) * 4;
         hipLaunchKernelGGL((heatmaps_to_pairs_kernel<_Float16, NF>), dim3((unsigned)((total + 255) / 256)), dim3(256),

@@ -1021,6 +1021,12 @@ extern "C" int fvp_voxelize_plan(int kind, int otf, int cp, int B, int V, int J,
     return st;
 }
 
+// The choice launch_pairs makes (fvp_layout.h), for the tests: no GPU, no pointer dereferenced.
+extern "C" int fvp_pair_layout_kind(int nf, int W, unsigned long long heatmaps_addr) {
+    if ((nf != 1 && nf != 2 && nf != fvp::kPairFrames) || W < 2) return -1;
+    return (int)fvp::pair_layout_kind(nf, W, heatmaps_addr);
+}
+
 extern "C" int fvp_nchw_to_nhwc_f16(const void *in, int in_half, int N, int C, int H, int W, int Cp, void *out,
                                     void *stream) {
     if (!in || !out) return FVP_ERR_NULL;

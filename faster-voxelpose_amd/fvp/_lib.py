@@ -73,6 +73,7 @@ SIGNATURES = {
                                       c_void_p, ctypes.POINTER(GridSpec), ctypes.POINTER(ImageSpec), c_int, c_int,
                                       c_void_p, c_void_p, c_void_p],
     "fvp_voxelize_plan": [c_int] * 13 + [ctypes.POINTER(ctypes.c_longlong), c_int, ctypes.POINTER(c_int)],
+    "fvp_pair_layout_kind": [c_int, c_int, ctypes.c_ulonglong],
     "fvp_person_planes_cl_f16": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                  ctypes.POINTER(PersonSpec), c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                  c_void_p],

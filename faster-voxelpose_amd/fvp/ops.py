@@ -361,6 +361,15 @@ def voxelize_plan(kind: str, otf: bool, B: int, V: int, J: int, H: int, W: int, 
     return st, [GatherLaunch(*buf[i * nf:(i + 1) * nf]) for i in range(n.value)]
 
 
+PAIR_LAYOUTS = ("vec8", "rows", "entry")
+
+
+def pair_layout_kind(nf: int, W: int, address: int) -> int:
+    """fvp_pair_layout_kind (host only): the index into PAIR_LAYOUTS of the kernel that lays out the fp16
+    pair table of a chunk at `address` (tensor.data_ptr()) with nf frames per entry; -1: bad nf or W."""
+    return _lib.load().fvp_pair_layout_kind(int(nf), int(W), int(address))
+
+
 # ---------------------------------------------------------------------------
 @_custom_op("fvp::nms_topk", mutates_args=(), device_types="cuda")
 def nms_topk(prob: torch.Tensor, K: int) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:

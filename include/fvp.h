@@ -247,6 +247,17 @@ int fvp_voxelize_cl_cams_slab_f16(const void *heatmaps_cl, int cp, int B, int V,
 int fvp_voxelize_plan(int kind, int otf, int cp, int B, int V, int J, int H, int W, int X, int Y, int Z,
                       int has_grid_index, int cube_aligned, long long *plan, int cap, int *count);
 
+/* Which kernel lays out the fp16 pixel-pair table of a planar fp16 call with
+ * J <= 16 (host only; the function the launcher itself calls), for a chunk that
+ * starts at address heatmaps_addr with nf frames per table entry (record field 6
+ * of fvp_voxelize_plan: 4, 2 or 1) and heatmaps W wide:
+ *   0  8 entries per thread (W % 8 == 0 and a 16-B aligned address)
+ *   1  one block per row through LDS (nf > 1, W even, a 4-B aligned address and
+ *      nf * 16 * (W / 2 + 2) * 4 <= 65536 bytes of LDS)
+ *   2  one thread per entry (everything else)
+ * -1 for nf other than 1, 2, 4 or W < 2. */
+int fvp_pair_layout_kind(int nf, int W, unsigned long long heatmaps_addr);
+
 /* Peak NMS + top-K on a [B,1,X,Y] map: 3x3 max-pool keep mask, top-K of the
  * masked map (value descending, flat index ascending on ties), and
  * get_index2D's (flat // X, flat % X) decode.

@@ -57,6 +57,9 @@ def test_argument_validation_without_gpu():
         del os.environ["FVP_PAIR_FRAMES"]
     # fp16, J > 16: the fp32 channels-last copy
     assert lib.fvp_voxelize_f16_workspace_bytes(1, 5, 17, 128, 240) == 5 * 128 * 240 * 32 * 4
+    # the pair table's layout kernel (host only): 0 vec8, 1 rows, 2 per entry; -1 for a bad nf or width
+    assert [lib.fvp_pair_layout_kind(4, w, a) for w, a in ((240, 0), (240, 4), (508, 4), (510, 4), (240, 2))] == [0, 1, 1, 2, 2]
+    assert lib.fvp_pair_layout_kind(3, 240, 0) == -1 and lib.fvp_pair_layout_kind(4, 1, 0) == -1
     assert lib.fvp_pack_grid(None, 5, 100, None, None) == 1001
     assert lib.fvp_pack_grid(1, 0, 100, 1, None) == 1002
     # packed grid of one sequence beyond 32-bit byte offsets

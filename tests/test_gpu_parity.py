@@ -520,6 +520,10 @@ def test_fp16_pair_layouts_agree(gpu_device, otf):
     assert hm_4.data_ptr() % 16 == 4 and hm.data_ptr() % 16 == 0 and hm.shape[-1] % 8 == 0
     c_r, x_r = layer.forward_fused(hm_4, {"seq": [seq] * 7}, cams, rt)
     assert torch.equal(cube, c_r) and torch.equal(xy, x_r)
+    # the three tensors take three different kernels (frames 0-3 at 4 per entry; the later groups start a
+    # multiple of 16 B further on)
+    from fvp import ops
+    assert [ops.pair_layout_kind(4, hm.shape[-1], t.data_ptr()) for t in (hm, hm_4, hm_odd)] == [0, 1, 2]
 
 
 def test_nms_on_channel_slice_without_copy(gpu_device):
