@@ -113,7 +113,7 @@ def project_grid(cams: torch.Tensor, resize_t: torch.Tensor, start: list[float],
 
 @project_grid.register_fake
 def _(cams, resize_t, start, end, center, bins, ori_max, img_w, img_h, hm_w, hm_h):
-    return cams.new_empty((cams.shape[0], bins[0] * bins[1] * bins[2], 2))
+    return cams.new_empty((cams.shape[0], bins[0] * bins[1] * bins[2], 2), dtype=torch.float32)
 
 
 # ---------------------------------------------------------------------------
@@ -135,7 +135,7 @@ def pack_grid(sample_grid: torch.Tensor) -> torch.Tensor:
 @pack_grid.register_fake
 def _(sample_grid):
     V, N = sample_grid.shape[0], sample_grid.shape[1]
-    return sample_grid.new_empty((N, grid_slots(V), 2))
+    return sample_grid.new_empty((N, grid_slots(V), 2), dtype=torch.float32)
 
 
 def packed_as_reference(packed: torch.Tensor, V: int) -> torch.Tensor:
@@ -230,15 +230,15 @@ def _(heatmaps, cams, grid_index, resize_t, start, end, center, bins, ori_max, i
       x_begin=0, x_end=-1):
     B, V, J = heatmaps.shape[:3]
     _, _, X, Y, Z = _x_rows(bins, x_begin, x_end)
-    return (heatmaps.new_empty((B, J, X, Y, Z) if want_cube else (0,)),
-            heatmaps.new_empty((B, J, X, Y) if want_xy else (0,)))
+    return (heatmaps.new_empty((B, J, X, Y, Z) if want_cube else (0,), dtype=torch.float32),
+            heatmaps.new_empty((B, J, X, Y) if want_xy else (0,), dtype=torch.float32))
 
 
 @voxelize.register_fake
 def _(heatmaps, packed_grids, grid_index, X, Y, Z, want_cube, want_xy):
     B, V, J = heatmaps.shape[:3]
-    return (heatmaps.new_empty((B, J, X, Y, Z) if want_cube else (0,)),
-            heatmaps.new_empty((B, J, X, Y) if want_xy else (0,)))
+    return (heatmaps.new_empty((B, J, X, Y, Z) if want_cube else (0,), dtype=torch.float32),
+            heatmaps.new_empty((B, J, X, Y) if want_xy else (0,), dtype=torch.float32))
 
 
 def _grid_index(grid_index: Optional[torch.Tensor], B: int, S: int, device) -> Optional[torch.Tensor]:
@@ -442,14 +442,15 @@ def nms_topk_columns(prob: torch.Tensor, K: int,
 @nms_topk_columns.register_fake
 def _(prob, K, cube):
     B = prob.shape[0]
-    return (prob.new_empty((B, K)), prob.new_empty((B, K, 2), dtype=torch.int64),
-            prob.new_empty((B, K), dtype=torch.int64), prob.new_empty((B, K, cube.shape[1], cube.shape[4])))
+    return (prob.new_empty((B, K), dtype=torch.float32), prob.new_empty((B, K, 2), dtype=torch.int64),
+            prob.new_empty((B, K), dtype=torch.int64),
+            prob.new_empty((B, K, cube.shape[1], cube.shape[4]), dtype=torch.float32))
 
 
 @nms_topk.register_fake
 def _(prob, K):
     B = prob.shape[0]
-    return (prob.new_empty((B, K)), prob.new_empty((B, K, 2), dtype=torch.int64),
+    return (prob.new_empty((B, K), dtype=torch.float32), prob.new_empty((B, K, 2), dtype=torch.int64),
             prob.new_empty((B, K), dtype=torch.int64))
 
 
@@ -470,7 +471,7 @@ def gather_columns(cube: torch.Tensor, flat: torch.Tensor) -> torch.Tensor:
 @gather_columns.register_fake
 def _(cube, flat):
     B, J, X, Y, Z = cube.shape
-    return cube.new_empty((B, flat.shape[1], J, Z))
+    return cube.new_empty((B, flat.shape[1], J, Z), dtype=torch.float32)
 
 
 @_custom_op("fvp::voxel_columns", mutates_args=(), device_types="cuda")
@@ -550,7 +551,7 @@ def gather_bbox(size: torch.Tensor, flat: torch.Tensor) -> torch.Tensor:
 
 @gather_bbox.register_fake
 def _(size, flat):
-    return size.new_empty((size.shape[0], flat.shape[1], 2))
+    return size.new_empty((size.shape[0], flat.shape[1], 2), dtype=torch.float32)
 
 
 @_custom_op("fvp::proposal_centers", mutates_args=(), device_types="cuda")
@@ -577,7 +578,7 @@ def proposal_centers(index: torch.Tensor, hm1d: Optional[torch.Tensor], confs: t
 
 @proposal_centers.register_fake
 def _(index, hm1d, confs, match_bbox, scale, bias, min_score):
-    return confs.new_empty((confs.shape[0], confs.shape[1], 7))
+    return confs.new_empty((confs.shape[0], confs.shape[1], 7), dtype=torch.float32)
 
 
 # ---------------------------------------------------------------------------
@@ -696,18 +697,18 @@ def person_planes_cams(heatmaps: torch.Tensor, cams: torch.Tensor, resize_t: tor
 def _(heatmaps, cams, resize_t, start, end, center, ori_max, img_w, img_h, proposals, frame_of, fine, scale, bias,
       whole_size, ind_size, bins, want_cubes, want_planes):
     P, J = proposals.shape[0], heatmaps.shape[2]
-    return (heatmaps.new_empty((P, J, bins[0], bins[1], bins[2]) if want_cubes else (0,)),
-            heatmaps.new_empty((3 * P, J, bins[0], bins[1]) if want_planes else (0,)),
-            heatmaps.new_empty((P, 3)))
+    return (heatmaps.new_empty((P, J, bins[0], bins[1], bins[2]) if want_cubes else (0,), dtype=torch.float32),
+            heatmaps.new_empty((3 * P, J, bins[0], bins[1]) if want_planes else (0,), dtype=torch.float32),
+            heatmaps.new_empty((P, 3), dtype=torch.float32))
 
 
 @person_planes.register_fake
 def _(heatmaps, fine_grid, proposals, frame_of, fine, scale, bias, whole_size, ind_size, bins, want_cubes,
       want_planes):
     P, J = proposals.shape[0], heatmaps.shape[2]
-    return (heatmaps.new_empty((P, J, bins[0], bins[1], bins[2]) if want_cubes else (0,)),
-            heatmaps.new_empty((3 * P, J, bins[0], bins[1]) if want_planes else (0,)),
-            heatmaps.new_empty((P, 3)))
+    return (heatmaps.new_empty((P, J, bins[0], bins[1], bins[2]) if want_cubes else (0,), dtype=torch.float32),
+            heatmaps.new_empty((3 * P, J, bins[0], bins[1]) if want_planes else (0,), dtype=torch.float32),
+            heatmaps.new_empty((P, 3), dtype=torch.float32))
 
 
 PERSON_KINDS = ("planar", "cams", "cl", "cl_f16")
@@ -746,7 +747,7 @@ def max_planes(cubes: torch.Tensor) -> torch.Tensor:
 @max_planes.register_fake
 def _(cubes):
     P, J, S = cubes.shape[:3]
-    return cubes.new_empty((3 * P, J, S, S))
+    return cubes.new_empty((3 * P, J, S, S), dtype=torch.float32)
 
 
 # ---------------------------------------------------------------------------
@@ -773,7 +774,8 @@ def soft_argmax(features: torch.Tensor, center_grid: torch.Tensor, offset: Optio
 @soft_argmax.register_fake
 def _(features, center_grid, offset, beta):
     P, J = features.shape[1], features.shape[2]
-    return features.new_empty((3, P, J, 2)), features.new_empty((3, P, J))
+    return (features.new_empty((3, P, J, 2), dtype=torch.float32),
+            features.new_empty((3, P, J), dtype=torch.float32))
 
 
 @_custom_op("fvp::fuse_poses", mutates_args=(), device_types="cuda")
@@ -794,7 +796,7 @@ def fuse_poses(pose: torch.Tensor, weights: torch.Tensor, maxprob: torch.Tensor)
 @fuse_poses.register_fake
 def _(pose, weights, maxprob):
     P, J = pose.shape[1], pose.shape[2]
-    return pose.new_empty((P, J, 3)), pose.new_empty((P,))
+    return pose.new_empty((P, J, 3), dtype=torch.float32), pose.new_empty((P,), dtype=torch.float32)
 
 
 def render_cp(J: int) -> int:
