@@ -335,6 +335,76 @@ __global__ __launch_bounds__(256) void scatter_poses_kernel(const long long *__r
     if (j == 0 && centers) centers[b * cs0 + k * cs1 + conf_col] = confs[p];
 }
 
+// The sync-free JLN route (no count read, fixed shapes): every (frame, proposal) slot p = b * K + k
+// in natural order instead of the selected ones.  Live slots copy their proposal row bit for bit;
+// dead slots get (0, 0, 0, 0, 0, -3, -3): with bbox = -3 person_window's margin is
+// int((1 - (-3)) / 2 * (bins - 1)) = 2 * (bins - 1) >= bins for bins >= 2, so start >= end on x and
+// y for any centre and the gather's blocks of that slot walk nothing (project_individual.py:262-275);
+// the centre is 0, not the dead slot's own values (NaN or huge ones must not reach rintf).
+__global__ __launch_bounds__(256) void pad_proposals_kernel(const unsigned char *__restrict__ mask, int n, int K,
+                                                            const float *__restrict__ rows, long long rs0,
+                                                            long long rs1, float *__restrict__ out,
+                                                            int *__restrict__ frame_of) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= n) return;
+    const int b = p / K, k = p - b * K;
+    float *__restrict__ o = out + (size_t)p * 7;
+    if (mask[p] != 0) {
+        const float *__restrict__ r = rows + (long long)b * rs0 + (long long)k * rs1;
+#pragma unroll
+        for (int q = 0; q < 7; ++q) o[q] = r[q];
+    } else {
+#pragma unroll
+        for (int q = 0; q < 5; ++q) o[q] = 0.0f;
+        o[5] = -3.0f;
+        o[6] = -3.0f;
+    }
+    if (frame_of) frame_of[p] = b;
+}
+
+// fuse_kernel and scatter_poses_kernel over the natural-order slots in one launch, masked on the
+// device: a live slot gets fuse_kernel's expressions in its operation order, its three plane poses
+// and (centers non-NULL) the maxprob mean in fuse_kernel's summation order; a dead slot gets +0.0
+// by selection (its inputs, computed from an empty window, may be anything) and its centers entry
+// is left alone.  Every output element is written, so nothing is pre-zeroed.
+__global__ __launch_bounds__(64) void fuse_scatter_kernel(const unsigned char *__restrict__ mask,
+                                                          const float *__restrict__ pose,
+                                                          const float *__restrict__ weights,
+                                                          const float *__restrict__ maxprob, int P, int J,
+                                                          float *__restrict__ all_fused, float *__restrict__ all_pose,
+                                                          float *__restrict__ centers, long long cs, int conf_col) {
+    const int p = blockIdx.x;
+    const size_t PJ = (size_t)P * J;
+    const bool live = mask[p] != 0;  // block-uniform
+    for (int j = threadIdx.x; j < J; j += 64) {
+        const size_t r = (size_t)p * J + j;
+        float *o = all_fused + r * 3;
+        float *oxy = all_pose + r * 2, *oxz = all_pose + (PJ + r) * 2, *oyz = all_pose + (2 * PJ + r) * 2;
+        if (live) {
+            const float wxy = weights[r], wxz = weights[PJ + r], wyz = weights[2 * PJ + r];
+            const float *xy = pose + r * 2, *xz = pose + (PJ + r) * 2, *yz = pose + (2 * PJ + r) * 2;
+            const float sx = wxy + wxz, sy = wxy + wyz, sz = wxz + wyz;
+            o[0] = (wxy / sx) * xy[0] + (wxz / sx) * xz[0];
+            o[1] = (wxy / sy) * xy[1] + (wyz / sy) * yz[0];
+            o[2] = (wxz / sz) * xz[1] + (wyz / sz) * yz[1];
+            oxy[0] = xy[0]; oxy[1] = xy[1];
+            oxz[0] = xz[0]; oxz[1] = xz[1];
+            oyz[0] = yz[0]; oyz[1] = yz[1];
+        } else {
+            o[0] = 0.0f; o[1] = 0.0f; o[2] = 0.0f;
+            oxy[0] = 0.0f; oxy[1] = 0.0f;
+            oxz[0] = 0.0f; oxz[1] = 0.0f;
+            oyz[0] = 0.0f; oyz[1] = 0.0f;
+        }
+    }
+    if (live && centers && threadIdx.x == 0) {
+        float s = 0.f;
+        for (int plane = 0; plane < 3; ++plane)
+            for (int j = 0; j < J; ++j) s += maxprob[(size_t)plane * PJ + (size_t)p * J + j];
+        centers[(long long)p * cs + conf_col] = s / (float)(3 * J);
+    }
+}
+
 }  // namespace fvp
 
 extern "C" int fvp_soft_argmax(const float *features, int P, int J, int S2, const float *center_grid,
@@ -415,5 +485,27 @@ extern "C" int fvp_scatter_poses(const long long *idx, int P, int B, int K, int 
     const long long n = (long long)P * J;
     hipLaunchKernelGGL(fvp::scatter_poses_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        idx, P, B, K, J, fused, pose, confs, all_fused, all_pose, centers, cs0, cs1, conf_col);
+    return (int)hipGetLastError();
+}
+
+extern "C" int fvp_pad_proposals(const unsigned char *mask, int B, int K, const float *rows, long long rs0,
+                                 long long rs1, float *out, int *frame_of, void *stream) {
+    if (B < 0 || K < 0 || (long long)B * K > (1LL << 24)) return FVP_ERR_SHAPE;
+    if (B == 0 || K == 0) return FVP_OK;
+    if (!mask || !rows || !out) return FVP_ERR_NULL;
+    const int n = B * K;
+    hipLaunchKernelGGL(fvp::pad_proposals_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       mask, n, K, rows, rs0, rs1, out, frame_of);
+    return (int)hipGetLastError();
+}
+
+extern "C" int fvp_fuse_scatter_poses(const unsigned char *mask, const float *pose, const float *weights,
+                                      const float *maxprob, int P, int J, float *all_fused, float *all_pose,
+                                      float *centers, long long cs, int conf_col, void *stream) {
+    if (P == 0) return FVP_OK;
+    if (!mask || !pose || !weights || !all_fused || !all_pose || (centers && !maxprob)) return FVP_ERR_NULL;
+    if (P < 0 || J <= 0) return FVP_ERR_SHAPE;
+    hipLaunchKernelGGL(fvp::fuse_scatter_kernel, dim3((unsigned)P), dim3(64), 0, (hipStream_t)stream, mask, pose,
+                       weights, maxprob, P, J, all_fused, all_pose, centers, cs, conf_col);
     return (int)hipGetLastError();
 }

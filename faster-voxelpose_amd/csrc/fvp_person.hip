@@ -503,6 +503,14 @@ extern "C" size_t fvp_person_workspace_bytes(int B, int V, int J, int H, int W) 
 
 namespace fvp {
 
+// +0.0 into the n floats of the planes a launch accumulates into: a grid-stride loop, one float
+// per lane and step (consecutive lanes store consecutive floats; 4-byte alignment is all that is
+// assumed of the planes).
+__global__ __launch_bounds__(256) void zero_planes_kernel(float *__restrict__ p, size_t n) {
+    const size_t step = (size_t)gridDim.x * 256;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += step) p[i] = 0.0f;
+}
+
 static int person_planes_any(const float *heatmaps, int cp, int B, int V, int J, int H, int W, const CoordSource &src,
                              const fvp_person_spec *spec, const float *proposals, const int32_t *frame_of, int P,
                              float *cubes, float *planes, float *offset, void *workspace, size_t workspace_bytes,
@@ -522,8 +530,23 @@ static int person_planes_any(const float *heatmaps, int cp, int B, int V, int J,
     const int SX = spec->bins[0], SY = spec->bins[1], SZ = spec->bins[2];
     if (pl.zeroed_planes) {
         const size_t n = pl.zeroed_planes * (size_t)P * J * SX * SY;
-        const hipError_t e = hipMemsetAsync(planes, 0, n * 4, st);
-        if (e != hipSuccess) return (int)e;
+        // A workaround, under a stream capture only: the zeroing goes in as a kernel node like its
+        // neighbours.  As a memset node, replays of a captured JLN after the first did not
+        // reproduce the eager planes; why the runtime's memset node does that is supposed, not
+        // established.  Eager launches keep the memset and pay one capture query.
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(st, &cap) != hipSuccess) {
+            (void)hipGetLastError();
+            cap = hipStreamCaptureStatusNone;
+        }
+        if (cap == hipStreamCaptureStatusActive) {
+            const size_t want = (n + 4 * 256 - 1) / (4 * 256);  // ~4 floats per lane, at most 4,096 blocks
+            const size_t blocks = want < 4096 ? want : 4096;
+            hipLaunchKernelGGL(zero_planes_kernel, dim3((unsigned)blocks), dim3(256), 0, st, planes, n);
+        } else {
+            const hipError_t e = hipMemsetAsync(planes, 0, n * 4, st);
+            if (e != hipSuccess) return (int)e;
+        }
     }
     const size_t HW = (size_t)H * W, S2 = (size_t)SX * SY, S3 = S2 * SZ;
     using TT = std::true_type;

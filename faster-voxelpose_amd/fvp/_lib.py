@@ -149,6 +149,10 @@ SIGNATURES = {
                         ctypes.c_longlong, c_int, c_void_p, c_void_p],
     "fvp_scatter_poses": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                           c_void_p, ctypes.c_longlong, ctypes.c_longlong, c_int, c_void_p],
+    "fvp_pad_proposals": [c_void_p, c_int, c_int, c_void_p, ctypes.c_longlong, ctypes.c_longlong, c_void_p, c_void_p,
+                          c_void_p],
+    "fvp_fuse_scatter_poses": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                               ctypes.c_longlong, c_int, c_void_p],
     "fvp_up2_head_nchw": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                           c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p],
     "fvp_render_keypoints": [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,

@@ -93,7 +93,17 @@ class FvpOptions:
       person path has no fp16 channels-last kernel and raises, so the option
       serves rigs whose JLN fine grid is cached -- up to 16 cameras at the
       reference's 253 x 253 x 64 fine grid (fvp.project_individual.PERSON_OTF_GRID_BYTES:
-      17 cameras and more go on the fly)."""
+      17 cameras and more go on the fly).
+    sync_free: fused_jln_forward reads nothing back from the device: all B*K
+      proposal slots run at fixed shapes (dead slots as empty windows in the
+      person gather, ProjectLayer.forward_all) and one launch fuses, scatters
+      and masks them (ops.fuse_scatter_poses), bit-identical to the synced route
+      on the live slots.  None = exactly when the current stream is being
+      captured (the synced route's count read cannot be recorded), so a whole
+      forward records into one fvp.graphs.CapturedStep; True = always (P2PNet then
+      runs 3*B*K planes instead of 3*(valid proposals): a latency route for
+      small batches); False = never, and a forward under capture raises
+      FvpError before any device read.  Eval mode, one sequence per batch."""
     cnn: bool = False
     cnn_dtype: torch.dtype = torch.float32
     backbone: bool = False
@@ -103,6 +113,7 @@ class FvpOptions:
     c2c_graphs: bool = True
     share_layout: bool = True
     heatmaps_dtype: torch.dtype = torch.float32
+    sync_free: bool | None = None
 
 
 DEFAULT_OPTIONS = FvpOptions()
@@ -133,7 +144,7 @@ def set_options(model, **changes) -> FvpOptions:
 
 
 def install(fused: bool = True, modules=None, cnn: bool = False, backbone: bool = False,
-            heatmaps_dtype: torch.dtype | None = None) -> dict:
+            heatmaps_dtype: torch.dtype | None = None, sync_free: bool | None = None) -> dict:
     """Patch the already-importable reference modules.  Returns what was patched.
 
     cnn=True (with fused=True): in eval mode the fused forwards run CenterNet,
@@ -143,11 +154,14 @@ def install(fused: bool = True, modules=None, cnn: bool = False, backbone: bool 
     relative).  backbone=True / "bf16": the same for the PoseResNet backbone.
     heatmaps_dtype=torch.float16: fp16 channels-last heatmaps written at their
     source (FvpOptions.heatmaps_dtype, with its limit); None = fp32.
+    sync_free: the JLN route without a host read (FvpOptions.sync_free); None =
+    under a stream capture only.
     These become the FvpOptions of the patched classes (per-model overrides:
     set_options)."""
     opts = FvpOptions(cnn=bool(cnn), cnn_dtype=torch.bfloat16 if cnn == "bf16" else torch.float32,
                       backbone=bool(backbone), backbone_dtype=torch.bfloat16 if backbone == "bf16" else torch.float32,
-                      heatmaps_dtype=_heatmaps_dtype(heatmaps_dtype))
+                      heatmaps_dtype=_heatmaps_dtype(heatmaps_dtype),
+                      sync_free=None if sync_free is None else bool(sync_free))
     mods = modules if modules is not None else sys.modules
     patched = {}
 

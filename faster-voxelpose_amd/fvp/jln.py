@@ -53,6 +53,10 @@ def fused_jln_forward(self, meta, heatmaps, proposal_centers, mask, cameras, res
         release_shared(heatmaps)
         return out
     device = heatmaps.device
+    if _wants_sync_free(self):
+        out = _jln_sync_free(self, meta, heatmaps, proposal_centers, mask, cameras, resize_transform)
+        release_shared(heatmaps)
+        return out
     B, K = proposal_centers.shape[:2]
     J = heatmaps.shape[2]
     all_fused = torch.zeros((B, K, J, 3), device=device)
@@ -70,6 +74,65 @@ def fused_jln_forward(self, meta, heatmaps, proposal_centers, mask, cameras, res
     # with its last consumer: it is not kept alive on the caller's tensor
     release_shared(heatmaps)
     return all_fused, all_pose
+
+
+def _wants_sync_free(self) -> bool:
+    """FvpOptions.sync_free: None = exactly under a stream capture (where the synced route's count
+    read cannot run); True / False = always / never -- never, under a capture, is an error raised
+    here, before anything reads the device."""
+    from . import _lib, integration
+
+    want = integration.options_of(self).sync_free
+    if want:
+        return True
+    capturing = torch.cuda.is_current_stream_capturing()
+    if want is None:
+        return capturing
+    if capturing:
+        raise _lib.FvpError("fvp: sync_free=False under a stream capture: the synced JLN route reads the number "
+                            "of valid proposals back to the host, which a capture cannot record (leave "
+                            "FvpOptions.sync_free at None or set it True)")
+    return False
+
+
+def _jln_sync_free(self, meta, heatmaps, proposal_centers, mask, cameras, resize_transform):
+    """The JLN with no host read and fixed shapes: all B*K (frame, proposal) slots go through the
+    person gather (dead slots as empty windows, ProjectLayer.forward_all), P2PNet, the soft-argmax
+    and WeightNet, and one launch fuses, scatters and masks them (ops.fuse_scatter_poses).  Per
+    live slot every step is the synced route's arithmetic on the same values, so the outputs are
+    the same bit for bit; the price is P2PNet on 3*B*K planes instead of 3*(valid proposals)."""
+    from . import _lib, cnn, integration
+
+    if not (isinstance(mask, torch.Tensor) and mask.is_cuda and mask.dim() == 2 and mask.dtype == torch.bool):
+        got = (f"{tuple(mask.shape)} {mask.dtype} on {mask.device}" if isinstance(mask, torch.Tensor)
+               else type(mask).__name__)
+        raise _lib.FvpError(f"fvp: the sync-free JLN route needs a 2-D bool device mask, got {got}")
+    if (proposal_centers.dtype != torch.float32 or proposal_centers.dim() != 3 or proposal_centers.stride(2) != 1
+            or tuple(proposal_centers.shape[:2]) != tuple(mask.shape)):
+        raise _lib.FvpError(f"fvp: the sync-free JLN route needs fp32 proposal centres [B, K, 7] with stride(2) == 1 "
+                            f"matching the mask, got {tuple(proposal_centers.shape)} {proposal_centers.dtype} strides "
+                            f"{proposal_centers.stride()}")
+    B = heatmaps.shape[0]
+    opts = integration.options_of(self)
+    use = opts.cnn and not self.conv_net.training
+    conv = cnn.cached(self.conv_net, opts.cnn_dtype) if use else self.conv_net
+    wnet = cnn.cached(self.weight_net) if use and not self.weight_net.training else self.weight_net
+    planes, offset, _ = self.project_layer.forward_all(heatmaps, meta, proposal_centers, mask, cameras,
+                                                       resize_transform)
+    P = planes.shape[0] // 3                                                        # B*K, dead slots included
+    J = heatmaps.shape[2]
+    if P == 0:
+        K = proposal_centers.shape[1]
+        return (torch.zeros((B, K, J, 3), device=heatmaps.device),
+                torch.zeros((3, B, K, J, 2), device=heatmaps.device))
+    out = conv(planes)                                                              # [3P,J,S,S]
+    features = out.reshape((3, P) + tuple(out.shape[1:]))                           # [3,P,J,S,S]
+    pose, maxprob = ops.soft_argmax(features, self.project_layer.center_grid, offset,
+                                    float(self.soft_argmax_layer.beta))
+    weights = wnet(features)                                                        # [3P,J,1]
+    if weights.dtype != torch.float32 or not weights.is_contiguous():
+        weights = weights.to(torch.float32).contiguous()
+    return ops.fuse_scatter_poses(mask, pose, weights, maxprob, proposal_centers, 4)
 
 
 def _jln_batch(self, meta, heatmaps, proposal_centers, mask, cameras, resize_transform, all_fused, all_pose, first):

@@ -1156,6 +1156,66 @@ def scatter_poses(idx: torch.Tensor, fused: torch.Tensor, pose: torch.Tensor, co
               _ptr(all_pose), _ptr(centers), centers.stride(0), centers.stride(1), conf_col, _stream(all_fused))
 
 
+def pad_proposals(mask: torch.Tensor, rows: torch.Tensor) -> tuple:
+    """(props [B*K, 7], frame_of [B*K] int32) for a [B, K] bool mask and rows [B, K, >= 7] float32
+    (last dim contiguous): EVERY (frame, proposal) slot in natural order, one launch and no host
+    read (fvp_pad_proposals) -- mask_select without the count.  A live slot is its row's first 7
+    values bit for bit; a dead slot is (0, 0, 0, 0, 0, -3, -3), whose window the per-person gather
+    skips for any grid with >= 2 bins per axis."""
+    if mask.dim() != 2 or mask.dtype != torch.bool or mask.device.type != "cuda":
+        raise _lib.FvpError(f"fvp: pad_proposals takes a 2-D bool device tensor, got {tuple(mask.shape)} {mask.dtype}")
+    if (rows.dim() != 3 or tuple(rows.shape[:2]) != tuple(mask.shape) or rows.shape[2] < 7
+            or rows.dtype != torch.float32 or rows.stride(2) != 1 or rows.device != mask.device):
+        raise _lib.FvpError(f"fvp: pad_proposals rows {tuple(rows.shape)} {rows.dtype} for a mask {tuple(mask.shape)}")
+    m = mask.contiguous()
+    B, K = m.shape
+    props = torch.empty((B * K, 7), dtype=torch.float32, device=m.device)
+    frame_of = torch.empty((B * K,), dtype=torch.int32, device=m.device)
+    if B * K == 0:
+        return props, frame_of
+    _lib.call("fvp_pad_proposals", _ptr(m), B, K, _ptr(rows), rows.stride(0), rows.stride(1), _ptr(props),
+              _ptr(frame_of), _stream(m))
+    return props, frame_of
+
+
+def fuse_scatter_poses(mask: torch.Tensor, pose: torch.Tensor, weights: torch.Tensor, maxprob: torch.Tensor,
+                       centers: Optional[torch.Tensor], conf_col: int = 4) -> tuple:
+    """fuse_poses + scatter_poses over all B*K natural-order slots in one launch, masked on the
+    device (fvp_fuse_scatter_poses): mask [B, K] bool, pose [3, B*K, J, 2], weights [3*B*K, J(, 1)],
+    maxprob [3, B*K, J] -> (all_fused [B, K, J, 3], all_pose [3, B, K, J, 2]).  Live slots are
+    fuse_poses' values bit for bit and centers[b, k, conf_col] (centers [B, K, W] float32 with
+    slots evenly strided, or None) receives their confidence; dead slots are +0.0 whatever their
+    inputs hold, and their centers entry is left alone."""
+    if mask.dim() != 2 or mask.dtype != torch.bool or mask.device.type != "cuda":
+        raise _lib.FvpError(f"fvp: fuse_scatter_poses takes a 2-D bool device mask, got {tuple(mask.shape)} "
+                            f"{mask.dtype}")
+    B, K = mask.shape
+    P = B * K
+    if pose.dim() != 4 or pose.shape[0] != 3 or pose.shape[1] != P or pose.shape[3] != 2:
+        raise _lib.FvpError(f"fvp: fuse_scatter_poses pose {tuple(pose.shape)} for {P} slots")
+    J = pose.shape[2]
+    for t, n, name in ((pose, 3 * P * J * 2, "pose"), (weights, 3 * P * J, "weights"), (maxprob, 3 * P * J, "maxprob")):
+        if t.numel() != n or t.dtype != torch.float32 or not t.is_contiguous() or t.device != mask.device:
+            raise _lib.FvpError(f"fvp: fuse_scatter_poses {name} {tuple(t.shape)} {t.dtype} must hold {n} contiguous "
+                                f"float32 values on {mask.device}")
+    cs = 0
+    if centers is not None:
+        if (centers.dim() != 3 or tuple(centers.shape[:2]) != (B, K) or centers.dtype != torch.float32
+                or centers.device != mask.device or not 0 <= conf_col < centers.shape[2] or centers.stride(2) != 1
+                or (B > 1 and K > 1 and centers.stride(0) != K * centers.stride(1))):
+            raise _lib.FvpError(f"fvp: fuse_scatter_poses centers {tuple(centers.shape)} {centers.dtype} strides "
+                                f"{centers.stride()} (evenly strided slots, column {conf_col})")
+        cs = centers.stride(1) if K > 1 or B <= 1 else centers.stride(0)
+    m = mask.contiguous()
+    all_fused = torch.empty((B, K, J, 3), dtype=torch.float32, device=m.device)
+    all_pose = torch.empty((3, B, K, J, 2), dtype=torch.float32, device=m.device)
+    if P == 0 or J == 0:
+        return all_fused, all_pose
+    _lib.call("fvp_fuse_scatter_poses", _ptr(m), _ptr(pose), _ptr(weights), _ptr(maxprob), P, J, _ptr(all_fused),
+              _ptr(all_pose), _ptr(centers), cs, int(conf_col), _stream(m))
+    return all_fused, all_pose
+
+
 def nms_topk_columns_joint(prob: torch.Tensor, K: int, cube: torch.Tensor):
     """nms_topk_columns with vals / flat in one buffer (proposal_buffers), so
     fvp.parallel.gather_proposals sends them as they are -- eager only: a

@@ -178,6 +178,28 @@ class ProjectLayer(nn.Module):
                                       proposal_centers, None, False, True)
         return planes, offset
 
+    def forward_all(self, heatmaps, meta, proposal_centers, mask, cameras, resize_transform):
+        """EVERY (frame, proposal) slot of the batch in one launch, with no host read: the
+        sync-free counterpart of forward_batch (no ``nonzero``, shapes fixed by B and K, so it
+        records into a stream capture).  proposal_centers [B,K,7] fp32, mask [B,K] bool.
+        Returns (planes [3*B*K,J,S,S] in natural slot order p = b*K + k, offset [B*K,3],
+        frame_of [B*K] int32).  A dead slot (mask false) is handed to the gather as the row
+        (0, 0, 0, 0, 0, -3, -3) of ops.pad_proposals: its window is empty on x and y for any
+        grid with >= 2 bins per axis, so its blocks walk nothing and its planes are zero.  One
+        rig per call: frames of several sequences raise."""
+        ops.forward_only(heatmaps, proposal_centers)
+        seqs = list(meta["seq"])[: heatmaps.shape[0]]
+        if len(set(seqs)) > 1:
+            raise _lib.FvpError(f"fvp: forward_all takes the frames of one sequence, got {len(set(seqs))}: the "
+                                f"fixed-shape route runs one launch on one rig's cameras")
+        SX, SY = (int(v) for v in self._const["ind_bins"][:2])
+        if SX < 2 or SY < 2:
+            raise _lib.FvpError(f"fvp: forward_all needs >= 2 person voxels on x and y, got {SX} x {SY}: with one "
+                                f"bin the dead slots' window is not empty")
+        props, frame_of = ops.pad_proposals(mask, proposal_centers)
+        _, planes, offset = self._run(heatmaps, 0, meta, cameras, resize_transform, props, frame_of, False, True)
+        return planes, offset, frame_of
+
     def forward_batch(self, heatmaps, meta, proposal_centers, mask, cameras, resize_transform, idx=None, sel=None):
         """Every valid proposal of the batch in one launch per sequence (the
         reference loops frames and proposals with host syncs,

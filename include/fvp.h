@@ -448,6 +448,29 @@ int fvp_mask_select(const unsigned char *mask, int rows, int cols, long long *id
 int fvp_scatter_poses(const long long *idx, int P, int B, int K, int J, const float *fused, const float *pose,
                       const float *confs, float *all_fused, float *all_pose, float *centers, long long cs0,
                       long long cs1, int conf_col, void *stream);
+/* The sync-free JLN route's selection (no count, nothing read back): every (frame, proposal) slot
+ * p = b * K + k in natural order instead of joint_localization_net.py:136-151's boolean selections.
+ *   mask device [B*K] uint8; rows device floats, row (b, k) at rows[b * rs0 + k * rs1 + 0 .. 7)
+ *   out [B*K][7]: a live slot's (mask != 0) row copied bit for bit, a dead slot's
+ *     (0, 0, 0, 0, 0, -3, -3) -- a bbox of -3 gives the per-person window a margin of
+ *     2 * (bins - 1) >= bins on x and y (bins >= 2), so start >= end for any centre and the gather
+ *     skips the slot (project_individual.py:262-275); the centre is 0, never the dead slot's own
+ *   frame_of [B*K] int32 or NULL: frame_of[p] = b
+ * B * K == 0 launches nothing. */
+int fvp_pad_proposals(const unsigned char *mask, int B, int K, const float *rows, long long rs0, long long rs1,
+                      float *out, int *frame_of, void *stream);
+/* fvp_fuse_poses and fvp_scatter_poses over the P = B*K natural-order slots in one launch, masked
+ * on the device (fuse_pose_preds, joint_localization_net.py:83-120, and the result scatters,
+ * :176-180); no output needs pre-zeroing:
+ *   live slot (mask[p] != 0): all_fused [P][J][3] = the fusion of pose [3][P][J][2] with
+ *     weights [3P][J], bit for bit as fvp_fuse_poses; all_pose [3][P][J][2] = pose; and (centers
+ *     non-NULL) centers[p * cs + conf_col] = mean of maxprob [3][P][J] as fvp_fuse_poses' confs
+ *   dead slot: all_fused and all_pose are +0.0 (selected: the inputs may be NaN or Inf), centers
+ *     is not touched
+ * cs: element stride between consecutive slots of centers.  P == 0 launches nothing. */
+int fvp_fuse_scatter_poses(const unsigned char *mask, const float *pose, const float *weights, const float *maxprob,
+                           int P, int J, float *all_fused, float *all_pose, float *centers, long long cs,
+                           int conf_col, void *stream);
 
 /* Dense 2-D convolution on the fp32 matrix cores (v_mfma_f32_32x32x2_f32),
  * implicit GEMM over NHWC activations, for the HDN / JLN CNNs
