@@ -177,6 +177,10 @@ SIGNATURES = {
                                c_void_p],
     "fvp_conv1x1_cl_f16": [c_void_p, ctypes.c_longlong, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int,
                            c_void_p, c_void_p],
+    "fvp_match_poses": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                        c_void_p, c_void_p],
+    "fvp_match_actors": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                         c_void_p, c_void_p, c_void_p],
 }
 
 ABI_VERSION = 22

@@ -32,6 +32,13 @@ bbox and z-column extraction (:191-192, :199-200) and one launch for the z
 pick and the test-mode ProposalLayer (:208-220).  Signatures, outputs and
 state_dict keys are unchanged, so run/validate.py and existing checkpoints
 work as before.
+
+With ``evaluate=True`` the last line of validate() (``loader.dataset.evaluate``,
+function.py:181) scores device predictions with fvp.evaluate:
+
+    dataset.panoptic.Panoptic.evaluate       -> fvp_panoptic_evaluate
+    dataset.shelf.Shelf.evaluate             -> fvp_shelf_evaluate
+    dataset.campus.Campus.evaluate           -> fvp_campus_evaluate
 """
 from __future__ import annotations
 
@@ -44,6 +51,7 @@ import torch
 from . import _lib
 from . import backbone as fvp_backbone
 from . import cnn as fvp_cnn
+from . import evaluate as fvp_evaluate
 from . import frames as fvp_frames
 from . import heatmaps as fvp_heatmaps
 from . import jln, project_individual, project_whole, proposal
@@ -144,7 +152,8 @@ def set_options(model, **changes) -> FvpOptions:
 
 
 def install(fused: bool = True, modules=None, cnn: bool = False, backbone: bool = False,
-            heatmaps_dtype: torch.dtype | None = None, sync_free: bool | None = None) -> dict:
+            heatmaps_dtype: torch.dtype | None = None, sync_free: bool | None = None,
+            evaluate: bool = False) -> dict:
     """Patch the already-importable reference modules.  Returns what was patched.
 
     cnn=True (with fused=True): in eval mode the fused forwards run CenterNet,
@@ -157,7 +166,13 @@ def install(fused: bool = True, modules=None, cnn: bool = False, backbone: bool 
     sync_free: the JLN route without a host read (FvpOptions.sync_free); None =
     under a stream capture only.
     These become the FvpOptions of the patched classes (per-model overrides:
-    set_options)."""
+    set_options).
+    evaluate=True: also patch ``evaluate`` of dataset.panoptic.Panoptic,
+    dataset.shelf.Shelf and dataset.campus.Campus (whichever is importable) to
+    score device predictions with fvp.evaluate: one matching launch over the
+    whole run instead of the per-frame loop, the ground truth built on first
+    use and kept on the dataset object; a CPU `preds` still takes the original
+    method (kept as ``_fvp_original_evaluate``).  Off by default."""
     opts = FvpOptions(cnn=bool(cnn), cnn_dtype=torch.bfloat16 if cnn == "bf16" else torch.float32,
                       backbone=bool(backbone), backbone_dtype=torch.bfloat16 if backbone == "bf16" else torch.float32,
                       heatmaps_dtype=_heatmaps_dtype(heatmaps_dtype),
@@ -212,7 +227,87 @@ def install(fused: bool = True, modules=None, cnn: bool = False, backbone: bool 
                 cls._fvp_original_forward = cls.forward
             cls.forward = jln.fused_jln_forward
             patched["models.joint_localization_net.JointLocalizationNet.forward"] = jln.fused_jln_forward
+    if evaluate:
+        for modname, cls, method in (("dataset.panoptic", "Panoptic", fvp_panoptic_evaluate),
+                                     ("dataset.shelf", "Shelf", fvp_shelf_evaluate),
+                                     ("dataset.campus", "Campus", fvp_campus_evaluate)):
+            m = mods.get(modname)
+            if m is not None and hasattr(m, cls):
+                c = getattr(m, cls)
+                if not hasattr(c, "_fvp_original_evaluate"):
+                    c._fvp_original_evaluate = c.evaluate
+                c.evaluate = method
+                patched[f"{modname}.{cls}.evaluate"] = method
     return patched
+
+
+def _on_device(preds) -> bool:
+    first = preds[0] if isinstance(preds, (list, tuple)) and len(preds) else preds
+    return isinstance(first, torch.Tensor) and first.is_cuda
+
+
+def _device_of(preds):
+    return (preds[0] if isinstance(preds, (list, tuple)) else preds).device
+
+
+def _cached_gt(dataset, device, build):
+    """The dataset's ground truth on `device`: built on first use, kept on the dataset object."""
+    cache = dataset.__dict__.setdefault("_fvp_evaluate_gt", {})
+    if device not in cache:
+        if "host" not in cache:
+            cache["host"] = build()
+        cache[device] = cache["host"].to(device)
+    return cache[device]
+
+
+def load_actor3d(path):
+    """actorsGT.mat's 'actor3D' as the object array [actor][frame] of [14, 3] poses
+    (empty where the actor is absent) that Shelf / Campus.evaluate index
+    (shelf.py:164-165): MATLAB's nested cells {1x1}{A x 1}{F x 1}, unwrapped."""
+    import numpy as np
+    import scipy.io as scio  # lazily: only Shelf / Campus scoring needs it (those reference modules import it)
+
+    def depth(c):
+        d = 0
+        while isinstance(c, np.ndarray) and c.dtype == object and c.size:
+            c, d = c.reshape(-1)[0], d + 1
+        return d
+
+    cell = scio.loadmat(path)["actor3D"]
+    while depth(cell) > 2 and cell.size == 1:
+        cell = cell.reshape(-1)[0]
+    actors = [np.asarray(a, dtype=object).reshape(-1) for a in cell.reshape(-1)]
+    out = np.empty((len(actors), len(actors[0])), dtype=object)
+    for a, frames in enumerate(actors):
+        out[a, :] = frames
+    return out
+
+
+def fvp_panoptic_evaluate(self, preds):
+    """Panoptic.evaluate (panoptic.py:214-265) on fvp.evaluate.panoptic; a CPU `preds` takes the reference's method."""
+    if not _on_device(preds):
+        return type(self)._fvp_original_evaluate(self, preds)
+    assert len(preds) == self.db_size, "number mismatch"
+    gt = _cached_gt(self, _device_of(preds), lambda: fvp_evaluate.PanopticGroundTruth.from_db(self.db))
+    return fvp_evaluate.panoptic(preds, gt)
+
+
+def _actors_evaluate(self, preds, recall_threshold, convert):
+    if not _on_device(preds):
+        return type(self)._fvp_original_evaluate(self, preds, recall_threshold)
+    gt = _cached_gt(self, _device_of(preds), lambda: fvp_evaluate.ActorGroundTruth.from_actor3d(
+        load_actor3d(os.path.join(self.dataset_dir, "actorsGT.mat")), self.frame_range))
+    return fvp_evaluate.pcp(preds, gt, convert, recall_threshold)
+
+
+def fvp_shelf_evaluate(self, preds, recall_threshold=500):
+    """Shelf.evaluate (shelf.py:162-227) on fvp.evaluate.pcp; a CPU `preds` takes the reference's method."""
+    return _actors_evaluate(self, preds, recall_threshold, fvp_evaluate.SHELF)
+
+
+def fvp_campus_evaluate(self, preds, recall_threshold=500):
+    """Campus.evaluate (campus.py:138-209) on fvp.evaluate.pcp; a CPU `preds` takes the reference's method."""
+    return _actors_evaluate(self, preds, recall_threshold, fvp_evaluate.CAMPUS)
 
 
 def center_net_from_xy(center_net, xy: torch.Tensor, opts: FvpOptions = DEFAULT_OPTIONS):

@@ -916,6 +916,53 @@ int fvp_render_poses3d_aug(const double *joints3d, const unsigned char *vis3d, c
 int fvp_conv1x1_cl_f16(const float *in, long long npix, int Cpi, const float *w, int ldw, int Cout,
                        const float *scale, const float *shift, int Cp, void *out_f16, void *stream);
 
+/* ---- scoring a run: the matching step of dataset.evaluate() ----------------------------
+ * Both calls cover every frame of a run in one launch on `stream`, allocate and
+ * synchronise nothing, and compute in float64 with every sum in index order (the
+ * reference's numpy sums are pairwise and its norms go through BLAS: values agree
+ * to a few ulp, discrete outputs exactly wherever the decision has a margin above
+ * that).  N == 0: FVP_OK, no launch.  FVP_ERR_NULL: any pointer missing;
+ * FVP_ERR_SHAPE: N < 0, another size <= 0, C < 5, or a size over its cap below. */
+#define FVP_EVAL_MAX_PAIRS 4096   /* K * G of fvp_match_poses (its pair means live in LDS) */
+#define FVP_EVAL_MAX_PREDS 64     /* K of fvp_match_actors (the converted poses live in LDS) */
+#define FVP_EVAL_MAX_ACTORS 32    /* A of fvp_match_actors */
+#define FVP_EVAL_MAX_CHANNELS 64  /* C, the per-joint record length of preds */
+
+/* Panoptic.evaluate's matching (lib/dataset/panoptic.py:220-245): every valid
+ * prediction against the ground-truth people of its frame.
+ *   preds      device [N][K][J][C] fp32: x, y, z, the valid flag at [..][0][3] (>= 0;
+ *              NaN is not valid), the score at [..][0][4]
+ *   gt         device [N][G][J][3] fp64;  gt_vis  device [N][G][J] uint8 (joints_3d_vis > 0.1)
+ *   num_person device [N] int32 (clamped to [0, G])
+ *   mpjpe fp64, gt_index int32, score fp32: device [N][K], every element written
+ * A slot counts iff num_person[i] > 0 and it is valid.  For one that counts:
+ * per person g < num_person[i] the mean, over the visible joints in index order,
+ * of the distance between the widened prediction and the ground truth (no
+ * visible joint: 0 / 0 = NaN, as np.mean of nothing); gt_index / mpjpe are
+ * np.argmin / np.min of those (the first NaN if there is one, otherwise the
+ * first minimum).  A slot that does not count: gt_index -1, mpjpe NaN.
+ * score = preds[i][k][0][4] either way.  J <= FVP_MAX_JOINTS. */
+int fvp_match_poses(const float *preds, int N, int K, int J, int C, const double *gt, const unsigned char *gt_vis,
+                    const int *num_person, int G, double *mpjpe, int *gt_index, float *score, void *stream);
+
+/* Shelf.evaluate / Campus.evaluate's matching and PCP part tests (lib/dataset/shelf.py:176-209,
+ * campus.py:153-190): every present actor against the valid predictions of its
+ * frame, converted to the 14-joint skeleton in the reference's mixed precision
+ * (convert 0: coco2shelf3D, shelf.py:230-256; 1: coco2campus3D, campus.py:212-230).
+ *   preds       device [N][K][17][C] fp32, as above
+ *   gt          device [N][A][14][3] fp64 (actor3D * 1000.0); rows of absent actors are not read
+ *   present     device [N][A] uint8
+ *   mpjpe fp64 / pred_index int32 / parts uint32: device [N][A];  valid_count int32: device [N]
+ * pred_index is the slot k of np.argmin over the valid predictions' 14-joint
+ * means (first NaN, else first minimum), mpjpe that mean; bit j of parts is set
+ * when part j of the matched prediction is correct: the nine limbs of
+ * shelf.py:170 in order, then the hip-centre to head-bottom part (:201-209), each
+ * (error_s + error_e) / 2 <= 0.5 * limb_length, false with a NaN.  An absent
+ * actor, or a frame with no valid prediction: pred_index -1, mpjpe NaN, parts 0.
+ * valid_count[i] is the number of valid predictions of frame i. */
+int fvp_match_actors(const float *preds, int N, int K, int C, const double *gt, const unsigned char *present, int A,
+                     int convert, double *mpjpe, int *pred_index, unsigned *parts, int *valid_count, void *stream);
+
 /* Roofline calibration (not on the product path): a float4 streaming copy of
  * `bytes` (multiple of 16) from src to dst; bench.py reports the op's HBM
  * rate as a fraction of this kernel's measured rate besides the nominal peak. */
